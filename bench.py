@@ -10,6 +10,11 @@ rank per iteration).
 
     python bench.py [--gpus N --steps K --warmup W]        (N > 1 without WORLD_SIZE: launches its own N ranks)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the
+line used to carry: the as-generated layout, repeats of the timed loop, per-kernel times and rooflines, render
+throughput, box calibration, HBM traffic under rocprofv3, the exchange report (N > 1), the densifying run, training
+quality and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -423,6 +428,50 @@ def touch_scene_run(dev, steps=3000, target=300_000, seeds=5000, W=1280, H=720, 
             "windows": windows}, views, (pts, cols)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def capture_outputs(model, perm, max_pixels=1 << 21, max_rows=1 << 16, seed=0):
+    """What the timed train step hands its caller after the last step, copied to the host as float32 / float64 arrays:
+    the rendered RGB and accumulated depth of that step's view, its two loss terms, and the parameters after that step's
+    optimizer update.  Parameter rows are taken in the scene generator's order (``perm``: the spatial sort's permutation,
+    new row i = generated row perm[i]), so that the files do not depend on the memory layout.  An image of more than
+    ``max_pixels`` pixels and a scene of more than ``max_rows`` Gaussians are cut to a fixed seeded sample of pixels /
+    Gaussians (1080p and an SH degree 3 sample: 46 MiB)."""
+    import numpy as np
+    last = model.last
+    loss = model.loss_from(last["tile_loss"], last["ssim_sum"], last["view"])
+    out = {"main_loss": np.float64(loss["main_loss"].item()), "depth_loss": np.float64(loss["depth_loss"].item())}
+    H, W = last["rgb"].shape[:2]
+    pix = None
+    if H * W > max_pixels:
+        pix = torch.randperm(H * W, generator=torch.Generator().manual_seed(seed + 1))[:max_pixels].sort().values
+    for name in ("rgb", "depth_acc"):
+        img = last[name].float().cpu()
+        out[name] = (img if pix is None else img.reshape(H * W, -1)[pix]).numpy()
+    p = model.params
+    rows = torch.arange(p.N)
+    if p.N > max_rows:
+        rows = torch.randperm(p.N, generator=torch.Generator().manual_seed(seed))[:max_rows].sort().values
+    if perm is not None:
+        inv = torch.empty_like(perm)
+        inv[perm] = torch.arange(perm.numel(), device=perm.device)
+        rows = inv.cpu()[rows]
+    for name in p.NAMES:
+        out[f"params_{name}"] = getattr(p, name)[rows.to(p.flat.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    return out
+
+
+def write_outputs(arrays, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def self_launch(n_ranks: int) -> int:
     """`python bench.py --gpus N` with N > 1 and no rank environment: start the N ranks through
     torch.distributed.run on 127.0.0.1 (a free port), pass their chatter to stderr and print exactly
@@ -487,6 +536,12 @@ def _main():
                     help="time the PyTorch-CPU oracle on the whole configs[1] frame (~3 min on 128 cores) instead of its centre quarter")
     ap.add_argument("--no-list-hint", action="store_true",
                     help="launch every sort class every frame (A/B of tgs_bin_sort's max_list_hint)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline loop also measure and check everything else the line reports (the options "
+                         "below that name a part of it apply under --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (image, depth, loss terms, a seeded sample of the updated "
+                         "parameters) as DIR/<name>.npy")
     ap.add_argument("--repeats", type=int, default=4, help="further runs of the timed loop after the headline one (value_repeats)")
     ap.add_argument("--no-calibration", action="store_true", help="skip the ~2 s box calibration block")
     ap.add_argument("--no-traffic-run", action="store_true",
@@ -528,6 +583,8 @@ def _main():
                     help="memory order of the Gaussians: morton = model.spatial_sort() at start-up (the "
                          "framework's default layout), asis = the order the scene generator emits (random)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     preset = CONFIGS[args.config]
@@ -545,7 +602,7 @@ def _main():
     from touch_gs_amd import ops, parallel
     from touch_gs_amd.model import DepthGaussianSplattingModel, ModelConfig
     from touch_gs_amd.optim import GaussianParams
-    from touch_gs_amd.scene import make_view, synthetic_gaussians
+    from touch_gs_amd.scene import make_views, synthetic_gaussians
 
     dp = parallel.init_from_env()
     if dp.world != args.gpus:
@@ -562,8 +619,8 @@ def _main():
                       depth_loss_type="DEPTH_UNCERTAINTY_WEIGHTED_LOSS", uncertainty_weight=1.0,
                       pipeline_ssim=args.ssim_pipeline)
     model = DepthGaussianSplattingModel(cfg, params)
-    views = [make_view(N, W, H, deg, args.seed, dev, view=v, n_views=args.views, clustered=clustered)
-             for v in range(args.views)]
+    # (the ground-truth scene is generated on the host once for all views: the same views as one make_view per view)
+    views, _ = make_views(N, W, H, deg, args.seed, dev, args.views, clustered=clustered)
     for v in views:
         v.valid_count()
     n_isect, n_need, n_longest = [], [], []
@@ -606,23 +663,28 @@ def _main():
         torch.cuda.synchronize()
         return dp.max_over_ranks(time.perf_counter() - t0)
 
-    value_asis = None
+    value_asis, perm = None, None
     if args.layout == "morton" and args.loop_only:
-        model.spatial_sort()
+        perm = model.spatial_sort()
     elif args.layout == "morton":
         # The framework keeps its Gaussians in 3-D Morton order (model.spatial_sort() at start-up and
         # after densification): a pure re-layout -- the train step computes the same thing on permuted
         # rows -- that lets the binning count per (group, tile).  The same measurement on the order the
-        # scene generator emits is reported next to it as `value_asis_layout`.
+        # scene generator emits is reported next to it as `value_asis_layout` (--full).  These steps run in
+        # every mode: the sort deals the long-run Gaussians of the cameras they rendered over the groups, so
+        # the layout the headline is quoted on depends on them.
         k_asis = min(args.steps, 50)
         value_asis = k_asis * dp.world / timed(min(args.warmup, 20), k_asis)
-        model.spatial_sort()
+        perm = model.spatial_sort()
     elapsed = timed(args.warmup, args.steps)
+    dumped = capture_outputs(model, perm) if args.dump_outputs and dp.rank == 0 else None
     # the same timed loop again, back to back (no further warm-up): `value` stays the FIRST loop -- what the driver's
     # contract times -- and `value_repeats` / `value_spread` say how far a 20-step loop after 5 warm-ups is from the
     # box's steady state (clock ramp, first-touch effects): VERDICT r5 next #6
-    rep_elapsed = [elapsed] + [timed(0, args.steps) for _ in range(max(args.repeats, 0))]
+    rep_elapsed = [elapsed] + ([timed(0, args.steps) for _ in range(max(args.repeats, 0))] if args.full else [])
     model.budget.check()  # raises if ANY timed frame overflowed its intersection buffer (sticky word)
+    if dumped is not None:
+        write_outputs(dumped, args.dump_outputs)
     replicas_identical = None
     if dp.world > 1:
         dp.assert_replicas_identical(model.params.flat)   # raises on divergence
@@ -637,10 +699,24 @@ def _main():
                    "config": {"workload": workload, "name": args.config, "layout": args.layout}})
         dp.barrier()
         return
+    head = {"metric": "train iters/s (whole-job views/s) + render Mpix/s, 1M Gaussians @ 1080p"
+                      if args.config == "cfg3" and not custom else "train iters/s (whole-job views/s) + render Mpix/s",
+            "value": round(value, 3), "unit": "iters/s",
+            "n_gpus": dp.world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload, "name": args.config if not custom else "custom",
+                       "gaussians": N, "width": W, "height": H, "sh_degree": deg, "views": args.views,
+                       "intersections": n_isect[0], "tiles": views[0].cam.num_tiles,
+                       "longest_tile_list_any_view": max(n_longest), "max_list_hint": model.budget.max_list_hint,
+                       "parallelism": f"dp{dp.world}",
+                       "layout": "morton (model.spatial_sort(): same scene, rows permuted)" if args.layout == "morton"
+                                 else "as generated (random order)",
+                       "depth_loss_type": cfg.depth_loss_type}}
 
     # ---- collective times of the exchange (outside the timed region; every rank takes part) ----
     comm = None
-    if dp.world > 1:
+    if dp.world > 1 and args.full:
         dp.timing = True
         for i in range(3):
             step(done[0]); done[0] += 1
@@ -650,7 +726,7 @@ def _main():
     # ranks walk the list in the same order).  A transport that fails (a peer wait that times out poisons its steps and
     # raises at the check) is reported with its error and the next one starts from a fresh PeerExchange.
     transports = None
-    if dp.world > 1 and args.dp_report:
+    if dp.world > 1 and args.full and args.dp_report:
         transports = {}
         first = (dp.transport, os.environ.get("TGS_PEER_SAFE_FLAGS", "1"))
         for name, tr, safe in (("rccl", "rccl", None), ("ipc_flags_behind_kernel_boundary", "ipc", "1"),
@@ -683,13 +759,13 @@ def _main():
     # message-size sweep of the exchange primitives on this job's ranks (every rank takes part): replaces the link
     # figures assumed in DESIGN.md section 6 by measurements the moment a multi-GPU node runs this
     busbw = None
-    if dp.world > 1 and not args.no_busbw_sweep:
+    if dp.world > 1 and args.full and not args.no_busbw_sweep:
         dp.check_transport()
         busbw = dp.busbw_sweep(dev)
 
     # ---- per-kernel timing of the same step (HIP events on the launch stream), rank 0 ----
-    out = None
-    if dp.rank == 0:
+    out = head if dp.rank == 0 else None
+    if dp.rank == 0 and args.full:
         ev = lambda: torch.cuda.Event(enable_timing=True)
         names = ["project_bin_sort", "raster_fwd", "ssim", "raster_bwd", "project_bwd", "adam"]
         reps = min(args.steps, 20)
@@ -804,25 +880,13 @@ def _main():
         fwd_bwd_ms = sum(kern_ms[k] for k in names[:5] if k != "ssim")
         fwd_bwd_bytes = sum(sb[k] for k in names[:5] if k != "ssim")
         out = {
-            "metric": "train iters/s (whole-job views/s) + render Mpix/s, 1M Gaussians @ 1080p"
-                      if args.config == "cfg3" and not custom else "train iters/s (whole-job views/s) + render Mpix/s",
-            "value": round(value, 3), "unit": "iters/s",
-            "n_gpus": dp.world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            **head,
             "value_repeats": [round(args.steps * dp.world / e, 2) for e in rep_elapsed],
             "value_spread": round((max(rep_elapsed) - min(rep_elapsed)) / sorted(rep_elapsed)[len(rep_elapsed) // 2], 4),
             "render_mpix_s": round(W * H / (render_ms * 1e-3) / 1e6, 1),
             "render_mpix_s_view_mean": round(W * H / (render_mean_ms * 1e-3) / 1e6, 1),
             "value_asis_layout": None if value_asis is None else round(value_asis, 3),
-            "config": {"workload": workload, "name": args.config if not custom else "custom",
-                       "gaussians": N, "width": W, "height": H, "sh_degree": deg, "views": args.views,
-                       "intersections": I, "tiles": T, "longest_tile_list": longest,
-                       "longest_tile_list_any_view": max(n_longest), "max_list_hint": model.budget.max_list_hint,
-                       "parallelism": f"dp{dp.world}",
-                       "layout": "morton (model.spatial_sort(): same scene, rows permuted)" if args.layout == "morton"
-                                 else "as generated (random order)",
-                       "depth_loss_type": cfg.depth_loss_type},
+            "config": {**head["config"], "longest_tile_list": longest},
             "kernel_ms": {k: round(v, 4) for k, v in kern_ms.items()},
             "kernel_ms_view_mean": {k: round(v, 4) for k, v in kern_ms_mean.items()},
             "intersections_view_mean": int(I_mean),

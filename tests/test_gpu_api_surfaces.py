@@ -1084,7 +1084,7 @@ def test_bench_two_gpus_rccl(dev, tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", free_port(), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "5", "--warmup", "2", "--config", "cfg2"],
+                        "--gpus", "2", "--steps", "5", "--warmup", "2", "--config", "cfg2", "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1105,7 +1105,7 @@ def test_bench_two_ranks_share_one_gpu(dev):
     env = dict(os.environ, TGS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", free_port(), os.path.join(root, "bench.py"),
-                        "--gpus", "2", "--steps", "4", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--dp-report"],
+                        "--gpus", "2", "--steps", "4", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--dp-report", "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert r.stdout.count("\n") == 1 and r.stdout.startswith("{"), r.stdout[:2000]   # ONE JSON line and nothing else on stdout
@@ -1132,7 +1132,7 @@ def test_bench_bare_command_launches_its_own_ranks(dev, transport):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--config", "cfg2"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                        "--config", "cfg2", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines          # nothing but the JSON line on stdout

@@ -19,7 +19,7 @@ def main():
         for tag, lib in (("A", a), ("B", b)):
             env = dict(os.environ, TGS_LIB_PATH=os.path.abspath(lib))
             out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "50",
-                                  "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                                  "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True, timeout=900)
             line = [l for l in out.stdout.splitlines() if l.startswith("{")]
             if not line:
                 print(tag, out.stderr[-400:], flush=True)

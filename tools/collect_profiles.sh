@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the judged profiles for cfg3 on the GPU box and writes them under gpurun_out/profiles_<tag>/:
-#   bench.json            -- `python bench.py` (un-profiled)
+#   bench.json            -- `python bench.py --full` (un-profiled)
 #   kernel_stats.csv      -- rocprofv3 --kernel-trace --stats of `bench.py --loop-only` (warm-up + the timed loop and
 #                            nothing else: 250 identical steps), so that its averages ARE the timed loop's
 #   reconcile.json        -- sum over kernels of (average x calls per step) next to ms_per_step of the same command,
@@ -14,7 +14,7 @@ TAG=${1:-rX}
 OUT=gpurun_out/profiles_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 rm -rf /tmp/prof_ks
 python bench.py --loop-only --steps 200 --warmup 50 2>/dev/null | grep "^{" > $OUT/bench_loop_only.json
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_ks -- python bench.py --loop-only --steps 200 --warmup 50 > /tmp/ks.log 2>&1

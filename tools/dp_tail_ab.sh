@@ -3,7 +3,7 @@
 #   bash tools/dp_tail_ab.sh <tag>   -> gpurun_out/<tag>_dp_fused_tail.json
 TAG=${1:-r6}; cd ${GRAFT_REPO_ROOT:-.}; mkdir -p gpurun_out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-B="--no-cpu-baseline --no-densify-run --train-quality off --no-traffic-run --no-calibration --no-busbw-sweep --steps 100 --warmup 30 --repeats 2"
+B="--full --no-cpu-baseline --no-densify-run --train-quality off --no-traffic-run --no-calibration --no-busbw-sweep --steps 100 --warmup 30 --repeats 2"
 python bench.py $B 2>/dev/null | tail -1 > /tmp/dp_single.json
 for m in 0 1 0 1; do
   TGS_DP_FORCE_COLLECTIVES=1 TGS_DP_FUSED_TAIL=$m python bench.py $B 2>/dev/null | tail -1 > /tmp/dp_w1_${m}_$RANDOM.json
