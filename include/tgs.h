@@ -268,8 +268,9 @@ int tgs_set_raster_variant(int k6_blocks_on, int k7_front_to_back);
  * evenly over K7's 4096 wave slots.  Defaults: factor 8 (object-centric scenes of 100 - 300 k Gaussians at 720p qualify:
  * K7 0.58 - 0.78 of its one-wave time; a uniform scene such as configs[2] or 1 M clustered Gaussians at 1080p do not),
  * min_walk 16 (48 until TGS_VERSION 310); environment TGS_K7_QUAD / TGS_K7_QUAD_MIN.  factor 0 = always one wave per tile; a negative argument
- * leaves that setting.  Returns factor | min_walk << 8 in effect.  Results of the two forms differ by the rounding
- * of one four-term sum per (tile, Gaussian). */
+ * leaves that setting.  Returns factor | min_walk << 8 in effect.  Ranges: factor 0 .. 255, min_walk 0 .. 2^23 - 1; larger
+ * values (arguments or environment) are clamped to them, so the packed value is never negative and decodes to the
+ * setting in force.  Results of the two forms differ by the rounding of one four-term sum per (tile, Gaussian). */
 int tgs_set_k7_quad(int factor, int min_walk);
 
 /* The LONGEST tiles of a chain-bound frame (TGS_VERSION 310; an EXPERIMENT, off by default: measured, the chain of the deepest
@@ -279,7 +280,8 @@ int tgs_set_k7_quad(int factor, int min_walk);
  * block in the lanes of a DPP row, transmittance and the sum behind as prefix scans.  min_walk 0 = off; negative arguments leave
  * a setting.  Environment TGS_K7_SCAN_MIN / TGS_K7_SCAN_HEADS; TGS_K7_SCAN_SIDE (default 1): the scan form's launch goes to an
  * internal stream beside the other launches of the call (fork / join by events on the caller's stream; one stream per process:
- * set 0 when several host threads call the backward concurrently).  Returns min_walk | heads << 16.  Same decisions; sums in
+ * set 0 when several host threads call the backward concurrently).  Returns min_walk | heads << 16.  Ranges: min_walk
+ * 0 .. 65535, heads 0 .. 32767; larger values (arguments or environment) are clamped to them.  Same decisions; sums in
  * scan order (rounding only). */
 int tgs_set_k7_scan(int min_walk, int heads);
 
@@ -302,7 +304,8 @@ int tgs_set_k6_split(int factor);
  * below 64) and `heads` = how many leading entries of the schedule get the three extra blocks (default 512, TGS_K6_HEADS).  An
  * object-centric 720p frame composites faster with factor 1, floor 128, 2048 heads (its mid-size lists are single waves on an
  * under-occupied GPU: -1.7 % of the step), uniform frames do not (-1 %): the trainer's re-sort switches between the two
- * (model.spatial_sort).  Negative arguments leave a setting; returns floor | heads << 16.  Bit-identical outputs. */
+ * (model.spatial_sort).  Negative arguments leave a setting; returns floor | heads << 16.  Ranges: floor 0 .. 65535, heads
+ * 0 .. 32767; larger values (arguments or environment) are clamped to them.  Bit-identical outputs. */
 int tgs_set_k6_split_shape(int floor, int heads);
 
 /* K7  compositing backward with the tactile depth/uncertainty loss fused in  (stands behind

@@ -608,6 +608,50 @@ def test_raster_defaults_are_process_wide_and_opts_override_them():
     assert (o.k6_blocks, o.k6_split, o.k7_front_to_back, o.k7_quad, o.k7_quad_min_walk) == (0, -1, -1, 0, -1)
 
 
+def test_packed_setters_round_trip_at_the_edges_of_their_fields():
+    """Every setter that packs two settings into one int returns (and its ops.* decoder reads back) exactly the setting in
+    force, at 0, 1, the largest value the packing holds and one past it (clamped to the largest): a field never spills
+    into its neighbour and the packed value is never negative (a negative field passed back would mean "leave it").
+    model.spatial_sort() and the test fixtures save and restore the settings through these return values."""
+    from touch_gs_amd import _lib, ops
+    lib = _lib.load()
+    # (C setter, ops decoder, (largest first field, largest second field), shift of the second field)
+    packed = {"k6_split_shape": (lib.tgs_set_k6_split_shape, ops.set_k6_split_shape, (65535, 32767), 16),
+              "k7_quad": (lib.tgs_set_k7_quad, ops.set_k7_quad, (255, (1 << 23) - 1), 8),
+              "k7_scan": (lib.tgs_set_k7_scan, ops.set_k7_scan, (65535, 32767), 16)}
+    before = {k: c(-1, -1) for k, (c, _, _, _) in packed.items()}
+    long_run_before = lib.tgs_set_long_run(-1)
+    try:
+        for name, (c_set, py_set, (hi0, hi1), shift) in packed.items():
+            mask = (1 << shift) - 1
+            for field, hi in ((0, hi0), (1, hi1)):
+                for v in (0, 1, hi, hi + 1, 40000, 1 << 30):
+                    want = min(v, hi)
+                    other = c_set(-1, -1)
+                    other = (other >> shift) if field == 0 else (other & mask)     # the field that must not move
+                    r = c_set(v, -1) if field == 0 else c_set(-1, v)
+                    exp = (want | other << shift) if field == 0 else (other | want << shift)
+                    assert r == exp and r >= 0, (name, field, v, r, exp)
+                    assert c_set(-1, -1) == exp, (name, field, v)
+                    got = py_set()
+                    assert got == ((want, other) if field == 0 else (other, want)), (name, field, v, got)
+                    # the decoded pair, passed back, sets the same thing
+                    assert py_set(*got) == got and c_set(-1, -1) == exp, (name, field, v)
+            # both fields at their largest at once
+            assert py_set(hi0 + 1, hi1 + 1) == (hi0, hi1) and c_set(-1, -1) == (hi0 | hi1 << shift), name
+        # the long-run threshold: 1 .. 256, < 1 leaves it
+        for v, want in ((1, 1), (2, 2), (256, 256), (257, 256), (1 << 30, 256)):
+            assert lib.tgs_set_long_run(v) == want and ops.set_long_run() == want, (v, want)
+        assert lib.tgs_set_long_run(0) == 256 and lib.tgs_set_long_run(-5) == 256
+    finally:
+        for name, (c_set, _, _, shift) in packed.items():
+            r = before[name]
+            c_set(r & ((1 << shift) - 1), r >> shift)
+        lib.tgs_set_long_run(long_run_before)
+    assert {k: c(-1, -1) for k, (c, _, _, _) in packed.items()} == before
+    assert lib.tgs_set_long_run(-1) == long_run_before
+
+
 def test_tile_start_copies_are_refused():
     """The rasterizer owns 512 scratch ints behind the tile starts; the Python ops refuse a tensor that
     has lost them (a clone of the T + 1 view) with the reason, before the C ABI's own length check would."""

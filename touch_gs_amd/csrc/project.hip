@@ -9,6 +9,7 @@
 // backward reads 44+12K+48 (+48*tiles_hit of partials) and writes 44+12K (+8) B per Gaussian.
 #include "tgs_adam.h"
 #include "tgs_binning.h"
+#include <cstddef>
 
 namespace {
 
@@ -508,8 +509,10 @@ struct RunScan {
   int base[TGS_GROUP];          // first pair index of the Gaussian's run (capacity < 2^31)
   int hits[TGS_GROUP];
   int wave_tot[TGS_GROUP / TGS_WAVE];
-  float seg_sum[2][16][12];     // the teams' results of a round, double buffered (10 of 12 used)
+  // the teams' results of a round, double buffered (10 of 12 used); read and written as float4 / float2
+  alignas(16) float seg_sum[2][16][12];
 };
+static_assert(offsetof(RunScan, seg_sum) % 16 == 0, "seg_sum is accessed through float4");
 
 template <int CTRL>
 __device__ __forceinline__ float row_dpp_add(float v) {

@@ -2234,28 +2234,31 @@ __global__ __launch_bounds__(1024) void k_raster_bwd_scan(
 // thread gives that launch the old or the new default, never a torn one.  Callers that need re-entrancy pass
 // TgsRasterOpts and leave the setters alone (tgs.h).
 #include <atomic>
+#include <climits>
+// `hi`: the largest value the field's setter can report in its packed return value (tgs.h); larger settings, from the
+// environment or a setter, are clamped to it.
 struct RasterDefault {
-  const char* env; int builtin; bool as_flag;
+  const char* env; int builtin; bool as_flag; int hi = INT_MAX;
   std::atomic<int> v{-1};
+  int clamp(int x) const { return as_flag ? (x != 0) : (x < 0 ? 0 : (x > hi ? hi : x)); }
   int get() {
     int x = v.load(std::memory_order_relaxed);
     if (x < 0) {
       const char* e = getenv(env);
-      x = e ? atoi(e) : builtin;
-      x = as_flag ? (x != 0) : (x < 0 ? 0 : x);
+      x = clamp(e ? atoi(e) : builtin);
       int expect = -1;
       if (!v.compare_exchange_strong(expect, x, std::memory_order_relaxed)) x = expect;   // a setter got there first
     }
     return x;
   }
-  void set(int x) { v.store(as_flag ? (x != 0) : x, std::memory_order_relaxed); }
+  void set(int x) { v.store(clamp(x), std::memory_order_relaxed); }
 };
 static RasterDefault g_k6_blocks{"TGS_K6_BLOCKS", 1, true};
 static RasterDefault g_k7_f2b{"TGS_K7_F2B", 0, true};
 // TGS_K7_QUAD: frame_is_chain_bound()'s factor (default 8: deepest walk beyond 4x the balanced per-slot load); 0 = one wave per tile always
-static RasterDefault g_k7_quad{"TGS_K7_QUAD", 8, false};
+static RasterDefault g_k7_quad{"TGS_K7_QUAD", 8, false, 255};
 // (round 6, same-box sweep on the saved 720p checkpoints, profiles/r6_ab_runs.txt: min_walk 48 -> 16: K7 263 -> 240 / 253 -> 232 us; flat below)
-static RasterDefault g_k7_quad_min{"TGS_K7_QUAD_MIN", 16, false};
+static RasterDefault g_k7_quad_min{"TGS_K7_QUAD_MIN", 16, false, (1 << 23) - 1};
 // TGS_K6_SPLIT: tile_is_split()'s factor (default 2: lists beyond 2x the balanced per-slot load, and 256); 0 = never.  Round 6 sweep
 // (profiles/r6_ab_runs.txt): 4 -> 2: K6 147 -> 108 / 134 -> 100 us on the 720p checkpoints, cfg3 unchanged (no tile qualifies),
 // 1 M clustered +1 %; factor 1 costs cfg3 9 %
@@ -2264,8 +2267,8 @@ static RasterDefault g_k6_split{"TGS_K6_SPLIT", 2, false};
 static RasterDefault g_k7_blocks{"TGS_K7_BLOCKS", 0, true};
 // TGS_K7_SCAN_MIN: tiles of a chain-bound frame that walk more than this many entries (among the schedule's first
 // TGS_K7_SCAN_HEADS slots) go to k_raster_bwd_scan on a second stream; 0 = off
-static RasterDefault g_k7_scan_min{"TGS_K7_SCAN_MIN", 0, false};
-static RasterDefault g_k7_scan_heads{"TGS_K7_SCAN_HEADS", 512, false};
+static RasterDefault g_k7_scan_min{"TGS_K7_SCAN_MIN", 0, false, 65535};
+static RasterDefault g_k7_scan_heads{"TGS_K7_SCAN_HEADS", 512, false, 32767};
 // TGS_K7_SCAN_SIDE: 1 (default) = the scan form's launch on an internal high-priority stream beside the four-wave launch
 // (fork / join by events: also legal inside a stream capture); 0 = in line on the caller's stream.  One stream and one
 // event pair per process: concurrent backward calls from several host threads must set this to 0.
@@ -2293,11 +2296,11 @@ extern "C" int tgs_set_raster_variant(int k6_blocks_on, int k7_front_to_back) {
 }
 // the split's shape: the shortest list it applies to (never below 64: one staged batch) and how many entries of the schedule
 // get extra blocks (tgs_set_k6_split_shape; the trainer widens both for object-centric models, model.spatial_sort)
-static RasterDefault g_k6_floor{"TGS_K6_FLOOR", 256, false};
-static RasterDefault g_k6_heads{"TGS_K6_HEADS", 512, false};
+static RasterDefault g_k6_floor{"TGS_K6_FLOOR", 256, false, 65535};
+static RasterDefault g_k6_heads{"TGS_K6_HEADS", 512, false, 32767};
 extern "C" int tgs_set_k6_split_shape(int floor, int heads) {
   if (floor >= 0) g_k6_floor.set(floor);
-  if (heads >= 0) g_k6_heads.set(heads > 65535 ? 65535 : heads);
+  if (heads >= 0) g_k6_heads.set(heads);
   return g_k6_floor.get() | (g_k6_heads.get() << 16);
 }
 extern "C" int tgs_set_k6_split(int factor) {
