@@ -25,7 +25,11 @@
 extern "C" {
 #endif
 
-#define TGS_VERSION 310         /* 0.3.1 -- 310 (additions only, nothing of 300 changed meaning): TgsRasterOpts gains a sixth field k7_blocks
+#define TGS_VERSION 320         /* 0.3.2 -- 320 (additions only, nothing of 310 changed meaning): TgsCamera gains a trailing long_run and
+                                   TgsRasterOpts gains k6_split_floor / k6_split_heads at its end (callers that pass the structs must pass the
+                                   new sizes; a zeroed long_run and -1 in the new fields keep the behaviour of 310): what the tgs_set_long_run /
+                                   tgs_set_k6_split_shape defaults choose for the process can now be chosen per call.
+                                   310 (additions only, nothing of 300 changed meaning): TgsRasterOpts gains a sixth field k7_blocks
                                    (callers that pass the struct must pass the new size), tgs_adam_sh_gathered_geom_project_next,
                                    tgs_calib_fma_stream.  300: every entry point that takes `tile_start` takes its length next to it (validated against
                                    tgs_tile_start_len: the rasterizer keeps 512 scratch ints behind the starts) and the rasterize calls declare it
@@ -55,6 +59,10 @@ typedef struct TgsCamera {
   float pix_center;   /* 0.5  */
   float bg[3];
   float glob_scale;   /* 1.0  */
+  int32_t long_run;   /* binning: a Gaussian whose rect holds more tiles than this is a long run (tgs_set_long_run).  0 = the
+                         process-wide default; otherwise clamped to 1 .. 256.  Not a camera property: it rides here because every
+                         entry point of the front half and K8 takes the block, and ONE frame must use one value throughout
+                         (TGS_VERSION 320) */
 } TgsCamera;
 
 /* Fused training loss evaluated inside the compositing backward:
@@ -220,6 +228,8 @@ typedef struct TgsRasterOpts {
   int32_t k7_quad;           /* chain-bound factor of the backward, 0 = one wave per tile (tgs_set_k7_quad) [TGS_K7_QUAD, 8] */
   int32_t k7_quad_min_walk;  /* walks up to this many entries stay with the one-wave kernel              [TGS_K7_QUAD_MIN, 16] */
   int32_t k7_blocks;         /* 1: backward in 4x4-block form (TGS_VERSION 310; measured, not the default) [TGS_K7_BLOCKS, 0] */
+  int32_t k6_split_floor;    /* shortest list the forward splits, never below 64 (tgs_set_k6_split_shape; TGS_VERSION 320) [TGS_K6_FLOOR, 256] */
+  int32_t k6_split_heads;    /* leading schedule entries that get the three extra blocks (same)          [TGS_K6_HEADS, 512] */
 } TgsRasterOpts;
 
 /* K6  per-tile front-to-back compositing of RGB + depth in ONE pass  (stands behind gsplat
@@ -287,11 +297,13 @@ int tgs_set_k7_scan(int min_walk, int heads);
 
 /* Binning: a Gaussian whose tile rect holds more than `tiles` tiles is a LONG RUN (TGS_VERSION 310): its pairs stay outside its
  * binning group's aggregated counting box (counted with direct atomics) and its partial-gradient records are summed by the
- * whole workgroup in K8 instead of by its own thread.  Default 32 (environment TGS_LONG_RUN); the trainer lowers it to 8 for
- * object-centric models, where a few thousand table / background Gaussians hold most of the pairs (model.spatial_sort; the
- * row order `optim.balanced_order` deals exactly these Gaussians evenly over the groups).  A launch-shape parameter: lists,
+ * whole workgroup in K8 instead of by its own thread.  Default 32 (environment TGS_LONG_RUN).  8 suits object-centric
+ * models, where a few thousand table / background Gaussians hold most of the pairs; the trainer chooses per model and passes
+ * its choice per call in TgsCamera.long_run (model.spatial_sort; the row order `optim.balanced_order` deals exactly these
+ * Gaussians evenly over the groups), which takes precedence over this default.  A launch-shape parameter: lists,
  * images and gradients are the same up to the rounding of K8's sums, whose shape depends on (tiles covered, this value).
- * tiles < 1 leaves the setting; returns the value in effect (1 .. 256).  Process-wide, like the other tgs_set_* tuning calls. */
+ * tiles < 1 leaves the setting; returns the value in effect (1 .. 256).  Process-wide, like the other tgs_set_* tuning calls:
+ * the default a TgsCamera with long_run = 0 falls back to. */
 int tgs_set_long_run(int tiles);
 
 /* The forward's counterpart for tiles with LONG lists: a tile whose list is longer than max(256, factor * I / 4096) --
@@ -303,8 +315,9 @@ int tgs_set_k6_split(int factor);
 /* The shape of that rule (TGS_VERSION 310): `floor` = the shortest list it splits (default 256, environment TGS_K6_FLOOR, never
  * below 64) and `heads` = how many leading entries of the schedule get the three extra blocks (default 512, TGS_K6_HEADS).  An
  * object-centric 720p frame composites faster with factor 1, floor 128, 2048 heads (its mid-size lists are single waves on an
- * under-occupied GPU: -1.7 % of the step), uniform frames do not (-1 %): the trainer's re-sort switches between the two
- * (model.spatial_sort).  Negative arguments leave a setting; returns floor | heads << 16.  Ranges: floor 0 .. 65535, heads
+ * under-occupied GPU: -1.7 % of the step), uniform frames do not (-1 %): the trainer's re-sort chooses per model and passes
+ * its choice per call (TgsRasterOpts.k6_split / k6_split_floor / k6_split_heads; model.spatial_sort); this call sets the
+ * process-wide defaults those fields fall back to.  Negative arguments leave a setting; returns floor | heads << 16.  Ranges: floor 0 .. 65535, heads
  * 0 .. 32767; larger values (arguments or environment) are clamped to them.  Bit-identical outputs. */
 int tgs_set_k6_split_shape(int floor, int heads);
 

@@ -30,7 +30,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/tgs.h but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature in touch_gs_amd/_lib.py"
     assert set(_lib.SIGNATURES) == set(syms)
-    assert lib.tgs_version() == 310
+    assert lib.tgs_version() == 320
 
 
 def _declared_prototypes():
@@ -80,12 +80,27 @@ def test_ctypes_signatures_match_the_header_prototypes():
         assert [kind(t) for t in argtypes] == protos[name], (name, [kind(t) for t in argtypes], protos[name])
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     from touch_gs_amd import _lib
-    assert C.sizeof(_lib.TgsCamera) == 16 * 4 + 4 * 4 + 2 * 4 + 2 * 4 + 3 * 4 + 4
+    assert C.sizeof(_lib.TgsCamera) == 16 * 4 + 4 * 4 + 2 * 4 + 2 * 4 + 3 * 4 + 4 + 4     # (+ long_run, TGS_VERSION 320)
     assert C.sizeof(_lib.TgsAdamSpec) == 11 * 4 + 4 + 8   # 11 floats, pad, device pointer
     assert C.sizeof(_lib.TgsLossSpec) == 3 * 8 + 4 * 4
-    assert C.sizeof(_lib.TgsRasterOpts) == 6 * 4
+    assert C.sizeof(_lib.TgsRasterOpts) == 8 * 4                                          # (+ k6_split_floor, k6_split_heads)
+    # what the C compiler makes of the header: the size of every struct and the offsets of the fields TGS_VERSION 320 added
+    structs = ("TgsCamera", "TgsLossSpec", "TgsAdamSpec", "TgsRasterOpts")
+    added = (("TgsCamera", "long_run"), ("TgsRasterOpts", "k6_split_floor"), ("TgsRasterOpts", "k6_split_heads"))
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "tgs.h"\nint main(void) { printf("%d", TGS_VERSION);'
+                   + "".join(f' printf(" %zu", sizeof({s}));' for s in structs)
+                   + "".join(f' printf(" %zu", offsetof({s}, {f}));' for s, f in added) + " return 0; }\n")
+    exe = tmp_path / "probe"
+    subprocess.check_call([os.environ.get("CC", "gcc"), "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    want = [320] + [C.sizeof(getattr(_lib, s)) for s in structs] + [getattr(getattr(_lib, s), f).offset for s, f in added]
+    assert got == want, (got, want)
+    # the grown structs only grew at their ends: the fields of TGS_VERSION 310 sit where they sat
+    assert _lib.TgsCamera.long_run.offset == 112 and _lib.TgsCamera.glob_scale.offset == 108
+    assert _lib.TgsRasterOpts.k7_blocks.offset == 20 and _lib.TgsRasterOpts.k6_split_floor.offset == 24
     # field order of the header (a per-call option read from the wrong slot would silently select another kernel form)
     txt = open(os.path.join(ROOT, "include", "tgs.h")).read()
     body = re.search(r"typedef struct TgsRasterOpts \{(.*?)\} TgsRasterOpts;", txt, flags=re.S).group(1)
@@ -603,16 +618,51 @@ def test_raster_defaults_are_process_wide_and_opts_override_them():
         lib.tgs_set_k6_split(before[1])
         lib.tgs_set_k7_quad(before[2] & 255, before[2] >> 8)
     o = ops.raster_opts()
-    assert [getattr(o, f[0]) for f in o._fields_] == [-1] * 6
+    assert [getattr(o, f[0]) for f in o._fields_] == [-1] * 8
     o = ops.raster_opts(k6_blocks=False, k7_quad=0)
     assert (o.k6_blocks, o.k6_split, o.k7_front_to_back, o.k7_quad, o.k7_quad_min_walk) == (0, -1, -1, 0, -1)
+    o = ops.raster_opts(k6_split=1, k6_split_floor=128, k6_split_heads=2048)
+    assert [getattr(o, f[0]) for f in o._fields_] == [-1, 1, -1, -1, -1, -1, 128, 2048]
+
+
+def test_camera_carries_the_long_run_threshold():
+    """Camera.long_run (0 = the process-wide default) reaches the C struct, survives downscaled(), and the model hands its
+    own rule to its launches through it -- one tuned camera object per source camera until the next re-sort (the prefetch
+    and the front buffers recognise their camera by identity) -- without touching a process-wide setting."""
+    from touch_gs_amd import Camera, _lib
+    from touch_gs_amd.model import DepthGaussianSplattingModel, ModelConfig, Tuning
+    from touch_gs_amd.optim import GaussianParams
+    lib = _lib.load()
+    cam = Camera(np.eye(4), 50.0, 50.0, 32.0, 32.0, 64, 64)
+    assert cam.long_run == 0 and cam.c_struct().long_run == 0
+    c8 = Camera(np.eye(4), 50.0, 50.0, 32.0, 32.0, 64, 64, long_run=8)
+    assert c8.c_struct().long_run == 8
+    d = c8.downscaled(2)
+    assert (d.W, d.H, d.long_run) == (32, 32, 8) and d.c_struct().long_run == 8
+    before = lib.tgs_set_long_run(-1), lib.tgs_set_k6_split(-1), lib.tgs_set_k6_split_shape(-1, -1)
+    m = DepthGaussianSplattingModel(ModelConfig(sh_degree=0), GaussianParams.allocate(512, 1, torch.device("cpu")))
+    assert m.tuning == Tuning() and m.tuned(cam) is cam                    # nothing chosen yet: the caller's camera as it is
+    o = m.tuning.raster_opts()
+    assert [getattr(o, f[0]) for f in o._fields_] == [-1] * 8
+    m.tuning = Tuning(long_run=8, k6_split=1, k6_split_floor=128, k6_split_heads=2048)
+    t = m.tuned(cam)
+    assert t is not cam and t.long_run == 8 and cam.long_run == 0 and m.tuned(cam) is t and m.tuned(c8) is c8
+    assert np.array_equal(t.viewmat, cam.viewmat) and (t.fx, t.W, t.bg) == (cam.fx, cam.W, cam.bg)
+    assert m.tuned(cam, keep=False) is t
+    other = Camera(np.eye(4), 50.0, 50.0, 32.0, 32.0, 64, 64)
+    assert m.tuned(other, keep=False).long_run == 8 and id(other) not in m._tuned_cams
+    o = m.tuning.raster_opts()
+    assert (o.k6_split, o.k6_split_floor, o.k6_split_heads, o.k7_quad) == (1, 128, 2048, -1)
+    assert m.spatial_sort().shape == (512,) and m.tuning.long_run == 8     # no frame seen: the rule stays, the memo goes
+    assert m._tuned_cams == {} and m.tuned(cam) is not t
+    assert (lib.tgs_set_long_run(-1), lib.tgs_set_k6_split(-1), lib.tgs_set_k6_split_shape(-1, -1)) == before
 
 
 def test_packed_setters_round_trip_at_the_edges_of_their_fields():
     """Every setter that packs two settings into one int returns (and its ops.* decoder reads back) exactly the setting in
     force, at 0, 1, the largest value the packing holds and one past it (clamped to the largest): a field never spills
     into its neighbour and the packed value is never negative (a negative field passed back would mean "leave it").
-    model.spatial_sort() and the test fixtures save and restore the settings through these return values."""
+    The test fixtures save and restore the settings through these return values."""
     from touch_gs_amd import _lib, ops
     lib = _lib.load()
     # (C setter, ops decoder, (largest first field, largest second field), shift of the second field)

@@ -756,7 +756,8 @@ OBJECT_VIEWS = (0, 1, 2)      # the cameras the trainer has rendered before its 
 
 
 def _settings():
-    """The process-wide tuning settings (tgs_set_*); model.spatial_sort() moves some of them for the whole process."""
+    """The process-wide tuning settings (tgs_set_*): the defaults of the per-call fields.  model.spatial_sort() leaves them
+    alone (its choice is the model's own record, model.tuning); the tests below move them for plain ops calls."""
     from touch_gs_amd import ops
     return dict(long_run=ops.set_long_run(), k6_split=ops.set_k6_split(), k6_split_shape=ops.set_k6_split_shape(),
                 k7_quad=ops.set_k7_quad(), k7_scan=ops.set_k7_scan(), raster_variant=ops.set_raster_variant())
@@ -775,7 +776,7 @@ def _apply(s):
 @pytest.fixture
 def process_settings():
     """Snapshot of the process-wide settings, restored after the test and checked to be back: without it every test
-    that runs later in the session would run under the re-sort's long run 8 and K6 factor 1 without knowing it."""
+    that runs later in the session would run under the long run 8 and K6 factor 1 these tests apply without knowing it."""
     before = _settings()
     yield before
     _apply(before)
@@ -784,8 +785,10 @@ def process_settings():
 
 def _trainer_resort(dev, deg):
     """prepare hook of build_case: the trainer's re-sort (model.spatial_sort) after steps on the OBJECT_VIEWS cameras.  It
-    chooses the process-wide settings and the row order; -> the permuted parameters and what it chose, with the tiles
-    per Gaussian it dealt the rows by (in the generated row order) and the plain Morton order for comparison."""
+    chooses the model's rules (model.tuning; the process-wide settings stay as they are: asserted) and the row order; ->
+    the permuted parameters and what it chose -- as the settings that make plain ops calls run under the same rules,
+    applied before returning (build_case drives plain ops calls; object_case restores) -- with the tiles per Gaussian it
+    dealt the rows by (in the generated row order) and the plain Morton order for comparison."""
     def prepare(P, intr, cam):
         from touch_gs_amd import ops
         from touch_gs_amd.model import DepthGaussianSplattingModel, ModelConfig
@@ -806,10 +809,28 @@ def _trainer_resort(dev, deg):
         rc = model.__dict__.setdefault("_recent_cams", collections.OrderedDict())
         for c in cams:
             rc[id(c)] = c
+        before = _settings()
         perm = model.spatial_sort().cpu().numpy()
+        assert _settings() == before, (before, _settings())
         Pp = {k: getattr(model.params, k).detach().cpu().clone() for k in GaussianParams.NAMES}
-        return Pp, dict(settings=_settings(), perm=perm, hits=hits, morton=mort)
+        chosen = _tuning_as_settings(model.tuning, before)
+        _apply(chosen)
+        return Pp, dict(settings=chosen, perm=perm, hits=hits, morton=mort)
     return prepare
+
+
+def _tuning_as_settings(t, base):
+    """A model's record (model.tuning) laid over the process-wide settings `base`: what _apply() must set for plain ops
+    calls to run under the model's rules (an entry the model leaves to the process default keeps `base`'s value)."""
+    s = dict(base)
+    if t.long_run:
+        s["long_run"] = t.long_run
+    if t.k6_split is not None:
+        s["k6_split"] = t.k6_split
+    floor, heads = base["k6_split_shape"]
+    s["k6_split_shape"] = (floor if t.k6_split_floor is None else t.k6_split_floor,
+                           heads if t.k6_split_heads is None else t.k6_split_heads)
+    return s
 
 
 def _object_longest(b):
@@ -968,3 +989,94 @@ def test_train_step_and_fused_adam_on_the_object_scene(object_case, dev, process
         _write_report(report)
         assert np.all(err <= tol), (tag, float((err / tol).max()), int(np.argmax(err / tol)))
         assert int((m != 0).sum()) > 0.5 * N
+
+
+# ---------------------------------------------------------------------------------------------
+# two models in one process: each runs under its own rules
+# ---------------------------------------------------------------------------------------------
+TWO_MODELS_OBJECT = (20_000, 1280, 720, 3, 97)     # object_720p's generator at a quarter of its Gaussians
+TWO_MODELS_UNIFORM = (20_000, 640, 400, 3, 31)
+TWO_MODELS_STEPS = 3                                # steps between two re-sorts
+
+
+def test_two_models_in_one_process_each_run_under_their_own_rules(dev, process_settings):
+    """An object-centric 720p model (object_720p's generator, 20 000 Gaussians: its re-sort picks long run 8 and K6 split
+    1 / 128 / 2048 -- asserted) and a uniform model (long run 32, K6 at the process defaults -- asserted) live in one
+    process.  Each is run ALONE from its initial state -- steps with the next view announced, a re-sort, steps, a re-sort,
+    steps -- and then both are run through the same programme INTERLEAVED step by step, re-sorts included: parameters and
+    both Adam moments of each model equal its solo run bit for bit, and the process-wide settings are never touched.
+    While the re-sort wrote its choice into process-wide state (TGS_VERSION 310) this failed: after the object model's
+    re-sort the uniform model's K8 sums ran under long run 8, and after the uniform model's re-sort the object model ran
+    under 32 -- a run's bits depended on which unrelated model had re-sorted last.  That the rule does reach the bits is
+    asserted here: the uniform model alone, with the process default moved to 8 under it, ends elsewhere."""
+    import itertools
+    import time
+    from touch_gs_amd import ops
+    from touch_gs_amd.model import DepthGaussianSplattingModel, ModelConfig, Tuning
+    from touch_gs_amd.optim import GaussianParams
+    from touch_gs_amd.scene import make_view, synthetic_gaussians
+    t0 = time.perf_counter()
+
+    def scene(cfg, clustered, mutate):
+        N, W, H, deg, seed = cfg
+        P, _ = synthetic_gaussians(N, W, H, deg, seed, clustered=clustered)
+        if mutate is not None:
+            mutate(P)
+        views = [make_view(N, W, H, deg, seed, dev, view=v, clustered=clustered) for v in OBJECT_VIEWS]
+        for v in views:
+            v.valid_count()
+        return {k: v.to(dev).contiguous() for k, v in P.items()}, views, deg
+
+    def fresh(sc):
+        D, views, deg = sc
+        params = GaussianParams.from_tensors(*[D[k].clone() for k in GaussianParams.NAMES])
+        return DepthGaussianSplattingModel(ModelConfig(sh_degree=deg, sh_degree_interval=0, spatial_sort=True), params), views
+
+    def programme(m, views):       # one model's life; yields after every step and every re-sort
+        m.spatial_sort()           # (start-up: no frame seen yet, plain Morton order, no rule chosen)
+        yield
+        for _ in range(3):
+            for i in range(TWO_MODELS_STEPS):
+                m.train_step(views[i % len(views)], next_view=views[(i + 1) % len(views)])
+                yield
+            m.spatial_sort()
+            yield
+
+    def state(m):
+        torch.cuda.synchronize()
+        return [t.clone() for t in (m.params.flat, m.optimizer.exp_avg, m.optimizer.exp_avg_sq)]
+
+    before = process_settings
+    sc_obj = scene(TWO_MODELS_OBJECT, True, _mutate_object)
+    sc_uni = scene(TWO_MODELS_UNIFORM, False, None)
+    want = {"object": Tuning(long_run=8, k6_split=1, k6_split_floor=128, k6_split_heads=2048), "uniform": Tuning(long_run=32)}
+    solo = {}
+    for name, sc in (("object", sc_obj), ("uniform", sc_uni)):
+        m, views = fresh(sc)
+        assert m.tuning == Tuning()
+        for _ in programme(m, views):
+            assert _settings() == before
+        assert m.tuning == want[name], (name, m.tuning)
+        solo[name] = state(m)
+    (a, va), (b, vb) = fresh(sc_obj), fresh(sc_uni)
+    for _ in itertools.zip_longest(programme(a, va), programme(b, vb)):
+        assert _settings() == before
+    assert a.tuning == want["object"] and b.tuning == want["uniform"], (a.tuning, b.tuning)
+    for name, m in (("object", a), ("uniform", b)):
+        for what, x, y in zip(("parameters", "exp_avg", "exp_avg_sq"), state(m), solo[name]):
+            assert torch.equal(x, y), (name, what, float((x - y).abs().max()))
+        assert bool(solo[name][1].any())          # (the steps did move the model)
+    # the rule is not a no-op for the uniform model: alone again, with the process default at 8 until its first rule
+    # (and so for the steps before its second re-sort), it ends elsewhere
+    try:
+        ops.set_long_run(8)
+        m, views = fresh(sc_uni)
+        for _ in programme(m, views):
+            pass
+        assert m.tuning == want["uniform"]
+        leaked = state(m)
+    finally:
+        _apply(before)
+    assert not all(torch.equal(x, y) for x, y in zip(leaked, solo["uniform"]))
+    assert _settings() == before
+    print(f"two models in one process: {time.perf_counter() - t0:.2f} s wall")

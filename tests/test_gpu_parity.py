@@ -628,10 +628,13 @@ def test_k6_quadrant_split_of_long_tiles_is_bit_identical(dev, want_idx):
     equal bit for bit to the unsplit launch, on an object-centric scene where the default rule splits the dense centre,
     with the rule forced onto every tile of the schedule's head (factor 1 at a tiny scene: lists > 256), and on a
     ragged image (width and height not multiples of 16).  The walk words K7's rule reads stay consistent: same maximum,
-    a sum within the quarter-rounding of the split tiles."""
+    a sum within the quarter-rounding of the split tiles.  The rule given PER CALL (raster_opts(k6_split, k6_split_floor,
+    k6_split_heads), process defaults untouched) equals the rule given through the two setters, outputs and walk words bit
+    for bit -- also in the shape the trainer picks for object-centric models (1 / 128 / 2048), which splits at least as many tiles."""
     from touch_gs_amd import ops
     from touch_gs_amd.scene import make_camera, synthetic_gaussians
     before = ops.set_k6_split()
+    shape_before = ops.set_k6_split_shape()
     try:
         for N, W, H, factor in ((60_000, 640, 400, 4), (30_000, 250, 170, 1)):
             P, intr = synthetic_gaussians(N, W, H, 3, 5, clustered=True)
@@ -656,8 +659,25 @@ def test_k6_quadrant_split_of_long_tiles_is_bit_identical(dev, want_idx):
             assert int(ww[0][:, 0].max()) == int(ww[1][:, 0].max()) > 0
             s0, s1 = int(ww[0][:, 1].sum()), int(ww[1][:, 1].sum())
             assert s0 > 0 and abs(s1 - s0) <= 0.5 * s0, (s0, s1)
+            # per call == setters: the rule of the loop above, and the object-centric shape
+            split_tiles = lambda f, floor, heads: int((torch.sort(n, descending=True).values[:heads] > max(floor, (I * f) >> 12)).sum())
+            assert split_tiles(1, 128, 2048) >= split_tiles(factor, *shape_before) > 0      # (tiles really are split)
+            for f, floor, heads in ((factor,) + shape_before, (1, 128, 2048)):
+                got = []
+                for per_call in (False, True):
+                    ops.set_k6_split(before if per_call else f)
+                    ops.set_k6_split_shape(*(shape_before if per_call else (floor, heads)))
+                    opts = ops.raster_opts(k6_split=f, k6_split_floor=floor, k6_split_heads=heads) if per_call else None
+                    torch.as_strided(ts, (8, 2), (64, 1), T + 1).zero_()
+                    out = ops.rasterize_fwd(cam, sp, sg, ts, want_idx=want_idx, opts=opts)
+                    got.append([o for o in out if o is not None] + [out[2].stop_pos, words()])
+                assert (ops.set_k6_split(), ops.set_k6_split_shape()) == (before, shape_before)
+                for a, b, c in zip(got[0], got[1], res[0] + [None]):
+                    assert torch.equal(a, b), (f, floor, heads)
+                    assert c is None or torch.equal(a, c), (f, floor, heads)      # (and both equal the unsplit launch)
     finally:
         ops.set_k6_split(before)
+        ops.set_k6_split_shape(*shape_before)
 
 
 def test_deterministic_bitwise(dev):
@@ -1047,7 +1067,9 @@ def test_long_run_threshold_changes_nothing_but_the_shape_of_the_sums(dev):
     """tgs_set_long_run (which Gaussians count as long runs: outside the group's counting box, their partial records
     summed by the whole workgroup in K8) is a launch-shape parameter: on an object-centric scene with screen-filling
     Gaussians the tile lists are the same bit for bit at 4, 8, 32 and 256 tiles, the images too, and the parameter
-    gradients agree to the rounding of K8's sums."""
+    gradients agree to the rounding of K8's sums.  The threshold given PER CALL (Camera.long_run, the process default
+    untouched) gives what the setter gives with a plain camera: lists, images and K8's outputs bit for bit."""
+    import dataclasses
     from touch_gs_amd import ops
     from touch_gs_amd.scene import make_camera, synthetic_gaussians
     N, W, H, deg = 40_000, 640, 400, 3
@@ -1059,19 +1081,28 @@ def test_long_run_threshold_changes_nothing_but_the_shape_of_the_sums(dev):
     v_rgb = torch.randn(H, W, 3, generator=g).to(dev)
     v_d, v_a = torch.randn(H, W, generator=g).to(dev), torch.randn(H, W, generator=g).to(dev)
     before = ops.set_long_run()
-    out = {}
+    out, per_call = {}, {}
+
+    def frame(cam):
+        sp, radii, gb, ts, sg, st = ops.project_bin_sort(cam, D["means"], D["log_scales"], D["quats"], D["opac_logit"], D["sh"], deg)
+        T = cam.num_tiles
+        n = int(ts[T])
+        rgb, depth, fT, _ = ops.rasterize_fwd(cam, sp, sg, ts)
+        partials, _ = ops.rasterize_bwd(cam, sp, gb, sg, ts, rgb, depth, fT, v_rgb, v_d, v_a)
+        grads = ops.project_bwd(cam, D["means"], D["log_scales"], D["quats"], D["opac_logit"], D["sh"], deg, sp, gb, partials)
+        return (ts[:T + 1].clone(), sg[:n].clone(), rgb.clone(), depth.clone(), [t.clone() for t in grads[:5]])
     try:
         for lr in (32, 4, 8, 256):
             assert ops.set_long_run(lr) == lr
-            sp, radii, gb, ts, sg, st = ops.project_bin_sort(cam, D["means"], D["log_scales"], D["quats"], D["opac_logit"], D["sh"], deg)
-            T = cam.num_tiles
-            n = int(ts[T])
-            rgb, depth, fT, _ = ops.rasterize_fwd(cam, sp, sg, ts)
-            partials, _ = ops.rasterize_bwd(cam, sp, gb, sg, ts, rgb, depth, fT, v_rgb, v_d, v_a)
-            grads = ops.project_bwd(cam, D["means"], D["log_scales"], D["quats"], D["opac_logit"], D["sh"], deg, sp, gb, partials)
-            out[lr] = (ts[:T + 1].clone(), sg[:n].clone(), rgb.clone(), depth.clone(), [t.clone() for t in grads[:5]])
+            out[lr] = frame(cam)
     finally:
         ops.set_long_run(before)
+    for lr in (32, 4, 8, 256):
+        per_call[lr] = frame(dataclasses.replace(cam, long_run=lr))
+        assert ops.set_long_run() == before
+        a, b = out[lr], per_call[lr]
+        assert all(torch.equal(x, y) for x, y in zip(a[:4], b[:4])), lr
+        assert all(torch.equal(x, y) for x, y in zip(a[4], b[4])), lr
     hits = (out[32][0][1:] - out[32][0][:-1])
     assert int(hits.max()) > 64
     for lr in (4, 8, 256):

@@ -8,7 +8,7 @@ The checkpoint holds the flat parameter buffer and every camera of the capture; 
 own renders from the training cameras (the capture's images do not travel: 64 MiB limit), slightly perturbed so that the
 loss and its gradients are not identically zero.  Kernel times do not depend on the image values.  The loop is the
 trainer's: speculative (sync-free) budget, next view announced (colour + front prefetch), fused K8 + Adam."""
-import argparse, json, os, sys, time
+import argparse, dataclasses, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
@@ -68,7 +68,7 @@ def breakdown(m, views, reps=5):
         rows.setdefault(name, []).append(round(e0.elapsed_time(e1) / reps * 1e3, 1))
         return r_
     for v in views:
-        cam, deg = v.cam, m.active_sh_degree()
+        cam, deg = m.tuned(v.cam), m.active_sh_degree()     # the plain ops below run under the model's own rules
         H, W = cam.H, cam.W
         b = ops.IntersectBudget()
         ops.project_bin_sort(cam, p_.means, p_.log_scales, p_.quats, p_.opac_logit, p_.sh, deg, b)
@@ -85,7 +85,7 @@ def breakdown(m, views, reps=5):
         rows.setdefault("pairs_in_those", []).append(int(hits[hits > 32].sum()))
         gh = torch.nn.functional.pad(hits, (0, (-len(hits)) % 256)).view(-1, 256).sum(1)
         rows.setdefault("largest_group_pairs", []).append(int(gh.max()))
-        rgb, dacc, fT, _ = T("k6_us", lambda: ops.rasterize_fwd(cam, splats, sg, ts))
+        rgb, dacc, fT, _ = T("k6_us", lambda: ops.rasterize_fwd(cam, splats, sg, ts, opts=m.tuning.raster_opts()))
         ss, vimg = T("ssim_us", lambda: ops.ssim_fwd_bwd(rgb, v.rgb, weight=-c_.ssim_lambda / (3 * H * W), reduce=False))
         parts, tl = T("k7_us", lambda: ops.rasterize_bwd(cam, splats, gb, sg, ts, rgb, dacc, fT, v_rgb=vimg, loss=m.loss_spec(v), want_tile_loss=True))
         T("k8_us", lambda: ops.project_bwd(cam, p_.means, p_.log_scales, p_.quats, p_.opac_logit, p_.sh, deg, splats, gb, parts, out=p_.grad_views(), want_v_xy=True))
@@ -117,7 +117,8 @@ def main():
         torch.cuda.synchronize()
     m.spatial_sort()
     out["layout"] = a.layout
-    out["long_run"] = ops.set_long_run()      # chosen by the re-sort (model.spatial_sort)
+    out["tuning"] = dataclasses.asdict(m.tuning)      # chosen by the re-sort (model.spatial_sort); None / 0 = process default
+    out["long_run"] = m.tuning.long_run
     if a.breakdown:
         out["breakdown"] = breakdown(m, views[:3])
     m.enable_speculative_budget()

@@ -19,7 +19,7 @@ class TgsCamera(C.Structure):
     _fields_ = [("viewmat", C.c_float * 16), ("fx", C.c_float), ("fy", C.c_float),
                 ("cx", C.c_float), ("cy", C.c_float), ("W", C.c_int32), ("H", C.c_int32),
                 ("near_plane", C.c_float), ("pix_center", C.c_float), ("bg", C.c_float * 3),
-                ("glob_scale", C.c_float)]
+                ("glob_scale", C.c_float), ("long_run", C.c_int32)]
 
 
 class TgsLossSpec(C.Structure):
@@ -31,7 +31,8 @@ class TgsLossSpec(C.Structure):
 class TgsRasterOpts(C.Structure):
     """Per-call choice of the compositing kernels' forms (tgs.h); -1 = the process-wide default."""
     _fields_ = [("k6_blocks", C.c_int32), ("k6_split", C.c_int32), ("k7_front_to_back", C.c_int32),
-                ("k7_quad", C.c_int32), ("k7_quad_min_walk", C.c_int32), ("k7_blocks", C.c_int32)]
+                ("k7_quad", C.c_int32), ("k7_quad_min_walk", C.c_int32), ("k7_blocks", C.c_int32),
+                ("k6_split_floor", C.c_int32), ("k6_split_heads", C.c_int32)]
 
 
 class TgsAdamSpec(C.Structure):

@@ -26,6 +26,9 @@ class Camera:
     pix_center: float = 0.5
     bg: Sequence[float] = (0.0, 0.0, 0.0)
     glob_scale: float = 1.0
+    # binning: Gaussians covering more tiles than this are long runs (TgsCamera.long_run); 0 = the process-wide default
+    # (TGS_LONG_RUN, 32).  A launch-shape choice of whoever renders with the camera (model.spatial_sort), not optics
+    long_run: int = 0
 
     def __post_init__(self):
         v = self.viewmat
@@ -75,4 +78,5 @@ class Camera:
         for i in range(3):
             c.bg[i] = float(self.bg[i])
         c.glob_scale = float(self.glob_scale)
+        c.long_run = int(self.long_run)
         return c

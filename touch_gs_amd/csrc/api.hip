@@ -35,21 +35,12 @@ __global__ __launch_bounds__(256) void k_calib_fma(int n_iter, float a, float b,
 }
 }  // namespace
 
-// Process-wide default of CamK.long_run (tgs_common.h make_camk): environment TGS_LONG_RUN once, tgs_set_long_run afterwards.
-#include <atomic>
+// Process-wide default of CamK.long_run (tgs_common.h make_camk; a TgsCamera with long_run > 0 overrides it per call).
 #include "tgs_binning.h"
 extern "C" int tgs_set_long_run(int tiles) {
-  static std::atomic<int> v{-1};
-  int x = v.load(std::memory_order_relaxed);
-  if (x < 0) {
-    const char* e = getenv("TGS_LONG_RUN");
-    int init = e ? atoi(e) : TGS_LONG_RUN;
-    init = init < 1 ? 1 : (init > 256 ? 256 : init);
-    int expect = -1;
-    x = v.compare_exchange_strong(expect, init, std::memory_order_relaxed) ? init : expect;
-  }
-  if (tiles >= 1) { x = tiles > 256 ? 256 : tiles; v.store(x, std::memory_order_relaxed); }
-  return x;
+  static TgsDefault g_long_run{"TGS_LONG_RUN", TGS_LONG_RUN, false, 256, 1};
+  if (tiles >= 1) g_long_run.set(tiles);
+  return g_long_run.get();
 }
 
 extern "C" int tgs_calib_fma_stream(int n_iter, float* sink, int64_t* n_wave_instr, void* stream) {

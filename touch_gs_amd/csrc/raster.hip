@@ -2229,50 +2229,27 @@ __global__ __launch_bounds__(1024) void k_raster_bwd_scan(
 
 }  // namespace
 
-// Process-wide DEFAULTS of the per-call TgsRasterOpts fields: read from the environment once (first use), settable
-// through the tgs_set_* calls afterwards (A/B runs, tests).  Atomic words, relaxed: a setter racing a launch on another
-// thread gives that launch the old or the new default, never a torn one.  Callers that need re-entrancy pass
-// TgsRasterOpts and leave the setters alone (tgs.h).
-#include <atomic>
-#include <climits>
-// `hi`: the largest value the field's setter can report in its packed return value (tgs.h); larger settings, from the
-// environment or a setter, are clamped to it.
-struct RasterDefault {
-  const char* env; int builtin; bool as_flag; int hi = INT_MAX;
-  std::atomic<int> v{-1};
-  int clamp(int x) const { return as_flag ? (x != 0) : (x < 0 ? 0 : (x > hi ? hi : x)); }
-  int get() {
-    int x = v.load(std::memory_order_relaxed);
-    if (x < 0) {
-      const char* e = getenv(env);
-      x = clamp(e ? atoi(e) : builtin);
-      int expect = -1;
-      if (!v.compare_exchange_strong(expect, x, std::memory_order_relaxed)) x = expect;   // a setter got there first
-    }
-    return x;
-  }
-  void set(int x) { v.store(clamp(x), std::memory_order_relaxed); }
-};
-static RasterDefault g_k6_blocks{"TGS_K6_BLOCKS", 1, true};
-static RasterDefault g_k7_f2b{"TGS_K7_F2B", 0, true};
+// Process-wide DEFAULTS of the per-call TgsRasterOpts fields (TgsDefault, tgs_common.h).
+static TgsDefault g_k6_blocks{"TGS_K6_BLOCKS", 1, true};
+static TgsDefault g_k7_f2b{"TGS_K7_F2B", 0, true};
 // TGS_K7_QUAD: frame_is_chain_bound()'s factor (default 8: deepest walk beyond 4x the balanced per-slot load); 0 = one wave per tile always
-static RasterDefault g_k7_quad{"TGS_K7_QUAD", 8, false, 255};
+static TgsDefault g_k7_quad{"TGS_K7_QUAD", 8, false, 255};
 // (round 6, same-box sweep on the saved 720p checkpoints, profiles/r6_ab_runs.txt: min_walk 48 -> 16: K7 263 -> 240 / 253 -> 232 us; flat below)
-static RasterDefault g_k7_quad_min{"TGS_K7_QUAD_MIN", 16, false, (1 << 23) - 1};
+static TgsDefault g_k7_quad_min{"TGS_K7_QUAD_MIN", 16, false, (1 << 23) - 1};
 // TGS_K6_SPLIT: tile_is_split()'s factor (default 2: lists beyond 2x the balanced per-slot load, and 256); 0 = never.  Round 6 sweep
 // (profiles/r6_ab_runs.txt): 4 -> 2: K6 147 -> 108 / 134 -> 100 us on the 720p checkpoints, cfg3 unchanged (no tile qualifies),
 // 1 M clustered +1 %; factor 1 costs cfg3 9 %
-static RasterDefault g_k6_split{"TGS_K6_SPLIT", 2, false};
+static TgsDefault g_k6_split{"TGS_K6_SPLIT", 2, false};
 // TGS_K7_BLOCKS: 1 = the backward in 4x4-block form (k_raster_bwd_blocks); default 0 (measured slower)
-static RasterDefault g_k7_blocks{"TGS_K7_BLOCKS", 0, true};
+static TgsDefault g_k7_blocks{"TGS_K7_BLOCKS", 0, true};
 // TGS_K7_SCAN_MIN: tiles of a chain-bound frame that walk more than this many entries (among the schedule's first
 // TGS_K7_SCAN_HEADS slots) go to k_raster_bwd_scan on a second stream; 0 = off
-static RasterDefault g_k7_scan_min{"TGS_K7_SCAN_MIN", 0, false, 65535};
-static RasterDefault g_k7_scan_heads{"TGS_K7_SCAN_HEADS", 512, false, 32767};
+static TgsDefault g_k7_scan_min{"TGS_K7_SCAN_MIN", 0, false, 65535};
+static TgsDefault g_k7_scan_heads{"TGS_K7_SCAN_HEADS", 512, false, 32767};
 // TGS_K7_SCAN_SIDE: 1 (default) = the scan form's launch on an internal high-priority stream beside the four-wave launch
 // (fork / join by events: also legal inside a stream capture); 0 = in line on the caller's stream.  One stream and one
 // event pair per process: concurrent backward calls from several host threads must set this to 0.
-static RasterDefault g_k7_scan_side{"TGS_K7_SCAN_SIDE", 1, true};
+static TgsDefault g_k7_scan_side{"TGS_K7_SCAN_SIDE", 1, true};
 struct ScanSide { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; bool ok = false; };
 static ScanSide& scan_side() {
   static ScanSide x = [] {
@@ -2286,7 +2263,7 @@ static ScanSide& scan_side() {
   }();
   return x;
 }
-static inline int opt_or(const TgsRasterOpts* o, int32_t TgsRasterOpts::*f, RasterDefault& d) {
+static inline int opt_or(const TgsRasterOpts* o, int32_t TgsRasterOpts::*f, TgsDefault& d) {
   return (o && o->*f >= 0) ? (int)(o->*f) : d.get();
 }
 extern "C" int tgs_set_raster_variant(int k6_blocks_on, int k7_front_to_back) {
@@ -2295,9 +2272,9 @@ extern "C" int tgs_set_raster_variant(int k6_blocks_on, int k7_front_to_back) {
   return (g_k6_blocks.get() ? 1 : 0) | (g_k7_f2b.get() ? 2 : 0);
 }
 // the split's shape: the shortest list it applies to (never below 64: one staged batch) and how many entries of the schedule
-// get extra blocks (tgs_set_k6_split_shape; the trainer widens both for object-centric models, model.spatial_sort)
-static RasterDefault g_k6_floor{"TGS_K6_FLOOR", 256, false, 65535};
-static RasterDefault g_k6_heads{"TGS_K6_HEADS", 512, false, 32767};
+// get extra blocks (tgs_set_k6_split_shape; the trainer widens both for object-centric models, per call: model.spatial_sort)
+static TgsDefault g_k6_floor{"TGS_K6_FLOOR", 256, false, 65535};
+static TgsDefault g_k6_heads{"TGS_K6_HEADS", 512, false, 32767};
 extern "C" int tgs_set_k6_split_shape(int floor, int heads) {
   if (floor >= 0) g_k6_floor.set(floor);
   if (heads >= 0) g_k6_heads.set(heads);
@@ -2350,8 +2327,8 @@ extern "C" int tgs_rasterize_fwd(const TgsCamera* cam, const float* splats,
     SplitRule sr;
     sr.factor = tile_order ? opt_or(opts, &TgsRasterOpts::k6_split, g_k6_split) : 0;
     sr.n_slots = grid;
-    sr.heads = sr.factor > 0 ? min(grid, g_k6_heads.get()) : 0;
-    sr.floor = max(64, g_k6_floor.get());
+    sr.heads = sr.factor > 0 ? min(grid, opt_or(opts, &TgsRasterOpts::k6_split_heads, g_k6_heads)) : 0;
+    sr.floor = max(64, opt_or(opts, &TgsRasterOpts::k6_split_floor, g_k6_floor));
     const int blocks = grid + 3 * sr.heads;
     if (final_idx)
       hipLaunchKernelGGL(k_raster_fwd_blocks<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, k, T, splats,

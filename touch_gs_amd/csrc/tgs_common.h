@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <atomic>
+#include <climits>
 #include "../../include/tgs.h"
 
 #define TGS_WAVE 64
@@ -98,13 +101,36 @@ struct CamK {
   float near_plane, pix_center, glob_scale;
   float bg[3];
   int W, H, TW, TH;
-  int long_run;    // binning: runs of more tiles than this are "long" (tgs_set_long_run; not a camera property -- it rides here because every kernel of the front half and K8 takes the block)
+  int long_run;    // binning: runs of more tiles than this are "long" (TgsCamera.long_run, else tgs_set_long_run; not a camera property -- it rides here because every kernel of the front half and K8 takes the block)
+};
+
+// A process-wide DEFAULT of a per-call tuning field (TgsRasterOpts, TgsCamera.long_run): read from the environment once
+// (first use), settable through its tgs_set_* call afterwards (A/B runs, tests), clamped to [lo, hi] either way.  An atomic
+// word, relaxed: a setter racing a launch on another thread gives that launch the old or the new default, never a torn
+// one.  Callers that need re-entrancy pass the per-call field and leave the setters alone (tgs.h).
+// `hi`: the largest value the field's setter can report in its (packed) return value (tgs.h).
+struct TgsDefault {
+  const char* env; int builtin; bool as_flag; int hi = INT_MAX; int lo = 0;
+  std::atomic<int> v{-1};
+  int clamp(int x) const { return as_flag ? (x != 0) : (x < lo ? lo : (x > hi ? hi : x)); }
+  int get() {
+    int x = v.load(std::memory_order_relaxed);
+    if (x < 0) {
+      const char* e = getenv(env);
+      x = clamp(e ? atoi(e) : builtin);
+      int expect = -1;
+      if (!v.compare_exchange_strong(expect, x, std::memory_order_relaxed)) x = expect;   // a setter got there first
+    }
+    return x;
+  }
+  void set(int x) { v.store(clamp(x), std::memory_order_relaxed); }
 };
 
 extern "C" int tgs_set_long_run(int tiles);
 static inline CamK make_camk(const TgsCamera* c) {
   CamK k;
-  k.long_run = tgs_set_long_run(-1);
+  // the one place where the frame's long-run threshold is resolved: the caller's, clamped as the setter clamps, else the default
+  k.long_run = c->long_run > 0 ? (c->long_run > 256 ? 256 : c->long_run) : tgs_set_long_run(-1);
   const float* V = c->viewmat;
   for (int r = 0; r < 3; r++) {
     for (int j = 0; j < 3; j++) k.R[3 * r + j] = V[4 * r + j];

@@ -73,7 +73,7 @@ class ModelConfig:
     # spatial_sort deals the Gaussians that covered more than 32 tiles in the last frame evenly over the binning groups
     # (optim.balanced_order): a layout choice like the Morton order itself, results unchanged
     balance_long_runs: bool = True
-    long_run: int = 0          # tiles beyond which a Gaussian is a long run (tgs_set_long_run); 0 = chosen at every re-sort (32, or 8 for object-centric frames)
+    long_run: int = 0          # tiles beyond which a Gaussian is a long run (Camera.long_run); 0 = chosen at every re-sort (32, or 8 for object-centric frames)
 
     def downscale_factor(self, step: int) -> int:
         """2 ** max(num_downscales - step // resolution_schedule, 0)  (Splatfacto._get_downscale_factor)."""
@@ -91,6 +91,20 @@ class ModelConfig:
     def lrs(self) -> Dict[str, float]:
         return dict(means=self.lr_means, log_scales=self.lr_scales, quats=self.lr_quats,
                     opac_logit=self.lr_opac, sh_dc=self.lr_sh_dc, sh_rest=self.lr_sh_rest)
+
+
+@dataclasses.dataclass(frozen=True)
+class Tuning:
+    """The launch-shape rules ONE model runs its kernels under, chosen by its re-sort (``spatial_sort``) and handed to
+    every launch the model issues: ``long_run`` in the camera (TgsCamera.long_run), the K6 split rule in the per-call
+    TgsRasterOpts.  0 / None = the process-wide default (environment, ``ops.set_*``), which the model never writes."""
+    long_run: int = 0
+    k6_split: Optional[int] = None
+    k6_split_floor: Optional[int] = None
+    k6_split_heads: Optional[int] = None
+
+    def raster_opts(self):
+        return ops.raster_opts(k6_split=self.k6_split, k6_split_floor=self.k6_split_floor, k6_split_heads=self.k6_split_heads)
 
 
 @dataclasses.dataclass
@@ -158,6 +172,23 @@ class DepthGaussianSplattingModel:
         self.front_prefetch = os.environ.get("TGS_FRONT_PREFETCH", "1") != "0"
         self._color_block = self._color_all = self._color_rows = None
         self.last = {}
+        self.tuning = Tuning()      # until the first re-sort that has seen a frame: the process defaults
+        self._tuned_cams = {}
+
+    def tuned(self, cam: Camera, keep: bool = True) -> Camera:
+        """``cam`` carrying this model's ``tuning.long_run``: what every launch of the model is given, so that K1's
+        counting box, ``k_fill_bins`` and K8's sums of one frame -- and the K1 a step runs for the NEXT view -- agree.
+        Memoised per camera object (the prefetch and the front buffers recognise their camera by identity) until the
+        next re-sort; ``keep=False`` for cameras that may never come back (rendering for evaluation)."""
+        lr = self.tuning.long_run
+        if lr == 0 or lr == cam.long_run:
+            return cam
+        hit = self._tuned_cams.get(id(cam))
+        if hit is None or hit[0] is not cam or hit[1].long_run != lr:
+            hit = (cam, dataclasses.replace(cam, long_run=lr))
+            if keep:
+                self._tuned_cams[id(cam)] = hit
+        return hit[1]
 
     @property
     def num_points(self) -> int:
@@ -178,7 +209,8 @@ class DepthGaussianSplattingModel:
         # sync-free training budget would turn an eval view that needs more pairs into background)
         budget = self.budget if self.budget.sync else self._sync_budget
         rgb, depth_acc, alpha, radii = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
-                                                  cam, deg, budget=budget)
+                                                  self.tuned(cam, keep=False), deg, budget=budget,
+                                                  opts=self.tuning.raster_opts())
         depth = depth_acc / torch.clamp(alpha, min=1e-10)
         return dict(rgb=rgb, depth=depth[..., None], accumulation=alpha[..., None],
                     depth_acc=depth_acc, alpha=alpha, radii=radii)
@@ -262,14 +294,14 @@ class DepthGaussianSplattingModel:
         """Forward + loss + backward of one view into ``params.grad`` (overwritten) -- or, with
         ``fuse_adam``, straight through the optimizer update (K8+K9 fused, ``params.grad`` untouched).
         No host sync unless ``budget.sync``.  Returns device tensors (l1+depth tile losses, ssim sum)."""
-        p, c, cam = self.params, self.config, view.cam
+        p, c, cam = self.params, self.config, self.tuned(view.cam)
         deg = self.active_sh_degree()
         H, W = cam.H, cam.W
         splats, radii, group_base, tile_start, sorted_gid, status = ops.project_bin_sort(
             cam, p.means, p.log_scales, p.quats, p.opac_logit, p.sh, deg, self.budget, want_radii=want_v_xy,
             colors=colors, next_front=next_front)
         guard = None if self.budget.sync else status   # overflowed frame => optimizer kernels are no-ops
-        rgb, depth_acc, fT, fidx = ops.rasterize_fwd(cam, splats, sorted_gid, tile_start)
+        rgb, depth_acc, fT, fidx = ops.rasterize_fwd(cam, splats, sorted_gid, tile_start, opts=self.tuning.raster_opts())
         v_img, ssim_sum = None, None
         if (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles
                 and not torch.cuda.is_current_stream_capturing()):
@@ -356,28 +388,22 @@ class DepthGaussianSplattingModel:
                 hits = (hits + int(n_cams) - 1) // int(n_cams)
             else:
                 hits = (hits + len(cams) - 1) // len(cams)    # mean tiles per view (rounded up)
-        long_run = ops.set_long_run()
         if hits is not None:
-            # which Gaussians count as long runs (tgs_set_long_run: the kernels' counting box, K8's shared sums AND the rows
+            # which Gaussians count as long runs (Camera.long_run: the kernels' counting box, K8's shared sums AND the rows
             # dealt over the groups here -- one number): 32 tiles, but 8 where the long runs ARE the frame -- an object on a
             # table: 7 % of the Gaussians hold 60 % of the pairs, and a group's pairs set the length of K1's counting,
             # k_fill_bins and K8 (largest group 8 951 -> 5 098 pairs, step -2.9 % / -2.2 % on the saved 720p checkpoints;
             # cfg3 -0.5 ... -1.3 % if it were applied there: profiles/r6_ab_runs.txt).  ModelConfig.long_run fixes it.
-            long_run = self.config.long_run
-            if long_run <= 0:
-                share = float(hits[hits > 32].sum()) / max(float(hits.sum()), 1.0)
-                long_run = 8 if share > 0.3 else 32
-            if long_run != ops.set_long_run():
-                ops.set_long_run(long_run)
-            if self.config.long_run <= 0:
-                # the same regime wants K6 to split more of its lists (tgs_set_k6_split_shape: -1.7 % of the step on the 720p
-                # checkpoints, +1 % on uniform frames); the process's own settings are kept for everything else
-                if getattr(self, "_k6_rule", None) is None:
-                    self._k6_rule = (ops.set_k6_split(), ops.set_k6_split_shape())
-                if share > 0.3:
-                    ops.set_k6_split(1); ops.set_k6_split_shape(128, 2048)
-                else:
-                    ops.set_k6_split(self._k6_rule[0]); ops.set_k6_split_shape(*self._k6_rule[1])
+            # The same regime wants K6 to split more of its lists (factor 1, floor 128, 2048 heads: -1.7 % of the step on the
+            # 720p checkpoints, +1 % on uniform frames, which keep the process's own settings).  The choice is THIS model's
+            # (self.tuning, carried by its cameras and raster options): nothing process-wide is written.
+            if self.config.long_run > 0:
+                self.tuning = Tuning(long_run=self.config.long_run)
+            elif float(hits[hits > 32].sum()) / max(float(hits.sum()), 1.0) > 0.3:
+                self.tuning = Tuning(long_run=8, k6_split=1, k6_split_floor=128, k6_split_heads=2048)
+            else:
+                self.tuning = Tuning(long_run=32)
+        long_run = self.tuning.long_run or 32     # (0 only while hits is None: plain Morton order, the value is not read)
         perm = balanced_order(self.params.means, hits, long_run=long_run)
         self.params.permute_(perm, self.optimizer.exp_avg, self.optimizer.exp_avg_sq)
         density = getattr(self, "density", None)
@@ -386,6 +412,7 @@ class DepthGaussianSplattingModel:
             density.vis_count = density.vis_count[perm]
             density.max_radius = density.max_radius[perm]
         self._graphs = {}
+        self._tuned_cams = {}
         self._prefetch_ready = None
         self._refines_since_sort = 0
         return perm
@@ -510,7 +537,7 @@ class DepthGaussianSplattingModel:
         for v in views:
             v.valid_count()
             b = ops.IntersectBudget()
-            ops.project_bin_sort(v.cam, p.means, p.log_scales, p.quats, p.opac_logit, p.sh, deg, b)
+            ops.project_bin_sort(self.tuned(v.cam), p.means, p.log_scales, p.quats, p.opac_logit, p.sh, deg, b)
             need = max(need, b.last_need)   # capacity under the per-XCD split, not the plain pair count
         self.budget = ops.IntersectBudget(capacity=int(need * headroom) + 4096, sync=False)
         self.budget.sticky_word(p.flat.device)   # allocated eagerly, outside the captured region
@@ -600,8 +627,10 @@ class DepthGaussianSplattingModel:
         # prefetched by the previous step: colours (+ front) from the fused optimizer kernel, or the front alone from
         # the geometry Adam of a data-parallel step
         colors = pre if (pre is not None and (fuse or (factored and pre.front_issued and not pre.colors_valid))
-                         and pre.matches(view.cam, self.params.N, deg)) else None
+                         and pre.matches(self.tuned(view.cam), self.params.N, deg)) else None
         arm = None
+        # the next view's K1 runs inside this step's optimizer kernel: under the rule its own step will run K8 with
+        next_cam = self.tuned(next_view.cam) if next_view is not None else None
         if fuse and next_view is not None and self.active_sh_degree(self.step + 1) == deg:
             bufs = getattr(self, "_prefetch_bufs", None)
             N, dev = self.params.N, self.params.flat.device
@@ -611,8 +640,8 @@ class DepthGaussianSplattingModel:
             # front prefetch: the optimizer kernel also runs the next view's K1 into that frame's buffers
             front = None
             if self.front_prefetch and not torch.cuda.is_current_stream_capturing():
-                front = ops.FrontBuffers(next_view.cam, N, self.budget.initial(N), density is not None, dev)
-            arm = (bufs[1] if colors is bufs[0] else bufs[0]).arm(next_view.cam, deg, front, self.budget)
+                front = ops.FrontBuffers(next_cam, N, self.budget.initial(N), density is not None, dev)
+            arm = (bufs[1] if colors is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget)
         if (factored and next_view is not None and self.front_prefetch
                 and self.active_sh_degree(self.step + 1) == deg):
             # data-parallel form of the front prefetch: the geometry Adam (last kernel of the step) also runs this
@@ -621,8 +650,8 @@ class DepthGaussianSplattingModel:
             bufs = getattr(self, "_prefetch_bufs", None)
             if bufs is None or bufs[0].N != N or bufs[0].colors.device != dev:
                 bufs = self._prefetch_bufs = [ops.ColorPrefetch(N, dev), ops.ColorPrefetch(N, dev)]
-            front = ops.FrontBuffers(next_view.cam, N, self.budget.initial(N), density is not None, dev)
-            arm = (bufs[1] if pre is bufs[0] else bufs[0]).arm(next_view.cam, deg, front, self.budget, colors_valid=False)
+            front = ops.FrontBuffers(next_cam, N, self.budget.initial(N), density is not None, dev)
+            arm = (bufs[1] if pre is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget, colors_valid=False)
         self.forward_backward(view, want_v_xy=density is not None, fuse_adam=fuse, color_block=block,
                               colors=colors, prefetch=arm if fuse else None,
                               next_front=arm.front if arm is not None else None)

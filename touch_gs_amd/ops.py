@@ -329,11 +329,14 @@ def _tile_start_len(tile_start) -> int:
     return tile_start.untyped_storage().nbytes() // 4 - tile_start.storage_offset()
 
 
-def raster_opts(k6_blocks=None, k6_split=None, k7_front_to_back=None, k7_quad=None, k7_quad_min_walk=None, k7_blocks=None):
+def raster_opts(k6_blocks=None, k6_split=None, k7_front_to_back=None, k7_quad=None, k7_quad_min_walk=None, k7_blocks=None,
+                k6_split_floor=None, k6_split_heads=None):
     """Per-call TgsRasterOpts (tgs.h): the forms of the compositing kernels for ONE rasterize_fwd / rasterize_bwd call,
-    independent of the process-wide ``set_raster_variant`` / ``set_k6_split`` / ``set_k7_quad`` defaults.  None = default."""
+    independent of the process-wide ``set_raster_variant`` / ``set_k6_split`` / ``set_k6_split_shape`` / ``set_k7_quad``
+    defaults.  None = default."""
     f = lambda v: -1 if v is None else int(v)
-    return _lib.TgsRasterOpts(f(k6_blocks), f(k6_split), f(k7_front_to_back), f(k7_quad), f(k7_quad_min_walk), f(k7_blocks))
+    return _lib.TgsRasterOpts(f(k6_blocks), f(k6_split), f(k7_front_to_back), f(k7_quad), f(k7_quad_min_walk), f(k7_blocks),
+                              f(k6_split_floor), f(k6_split_heads))
 
 
 def _check_tile_start(tile_start, T: int) -> None:
@@ -424,7 +427,8 @@ def set_k6_split_shape(floor: Optional[int] = None, heads: Optional[int] = None)
 
 def set_long_run(tiles: Optional[int] = None) -> int:
     """Binning: Gaussians covering more than ``tiles`` tiles are long runs (tgs_set_long_run; default 32, None = query):
-    counted outside the group's aggregated box, their partial records summed by the whole workgroup in K8."""
+    counted outside the group's aggregated box, their partial records summed by the whole workgroup in K8.  The
+    process-wide default of ``Camera.long_run`` = 0; a camera that carries its own value does not look at it."""
     return _lib.load().tgs_set_long_run(-1 if tiles is None else int(tiles))
 
 
@@ -609,13 +613,13 @@ def dp_agree_overflow(world: int, N: int, v_color_all, status_out, sticky=None):
 # ------------------------------------------------------------------------------------------------
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd=True):
+    def forward(ctx, means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd=True, opts=None):
         means, log_scales, quats, opac_logit, sh = map(_f32c, (means, log_scales, quats, opac_logit, sh))
         splats, radii, group_base, tile_start, sorted_gid, _ = project_bin_sort(
             cam, means, log_scales, quats, opac_logit, sh, sh_deg, budget, want_radii=True)
         # need_bwd = False: render only (evaluation, get_outputs under no_grad; decided by render(): grad mode is always
         # off in here and needs_input_grad ignores it) -- no backward will ask for the stop positions
-        rgb, depth, fT, fidx = rasterize_fwd(cam, splats, sorted_gid, tile_start, want_stop=need_bwd)
+        rgb, depth, fT, fidx = rasterize_fwd(cam, splats, sorted_gid, tile_start, want_stop=need_bwd, opts=opts)
         ctx.cam, ctx.sh_deg = cam, sh_deg
         ctx.want_xy = means2d is not None
         if need_bwd:
@@ -635,11 +639,11 @@ class _Render(torch.autograd.Function):
         v_means, v_ls, v_q, v_ol, v_sh, v_xy = project_bwd(
             cam, means, log_scales, quats, opac_logit, sh, ctx.sh_deg, splats, group_base, partials,
             want_v_xy=ctx.want_xy)
-        return v_means, v_ls, v_q, v_ol, v_sh, v_xy, None, None, None, None
+        return v_means, v_ls, v_q, v_ol, v_sh, v_xy, None, None, None, None, None
 
 
 def render(means, log_scales, quats, opac_logit, sh, cam: Camera, sh_deg: int,
-           means2d: Optional[torch.Tensor] = None, budget: Optional[IntersectBudget] = None):
+           means2d: Optional[torch.Tensor] = None, budget: Optional[IntersectBudget] = None, opts=None):
     """Fused differentiable render of RGB + depth + alpha in one compositing pass.
 
     Parameters are the raw (pre-activation) Gaussian parameters of SURVEY App. B.0.
@@ -647,10 +651,11 @@ def render(means, log_scales, quats, opac_logit, sh, cam: Camera, sh_deg: int,
     (INRIA ``means2D.grad`` convention) for densification statistics.
     Returns (rgb [H,W,3] incl. background, depth_acc [H,W] = sum w*z, alpha [H,W], radii [N]).
     Expected depth is ``depth_acc / alpha`` (consumer side, as Splatfacto does).
+    ``opts`` = ``raster_opts(...)`` for the forward of this call only.
     """
     need_bwd = torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                for t in (means, log_scales, quats, opac_logit, sh, means2d))
-    return _Render.apply(means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd)
+    return _Render.apply(means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd, opts)
 
 
 # ------------------------------------------------------------------------------------------------
