@@ -262,6 +262,29 @@ int tgs_rasterize_fwd(const TgsCamera* cam /*[host]*/, const float* splats,
  * evaluations; the results are bit-identical with and without it. */
 size_t tgs_slot_ok_len(int W, int H, int64_t capacity);
 
+/* K6s per-pixel depth statistics of a composited frame (an ADDITION within TGS_VERSION 320: no struct and no earlier
+ *     signature changed).  Forward only, no gradients.  Walks the lists a tgs_rasterize_fwd composited once more, with the
+ *     forward's arithmetic on the same bits -- every pixel includes exactly the entries the forward included, with the
+ *     same weights w = alpha T -- and needs that forward's images:
+ * in : splats, sorted_gid, tile_start, tile_order (may be NULL; scheduling only) as given to tgs_rasterize_fwd;
+ *      out_depth[H,W] (= sum w d), final_T[H,W] of that forward; stop_pos[H,W] of that forward or NULL (it only bounds
+ *      the walk: the outputs are bit-identical with and without it)
+ * out: depth_var[H,W]     sum w (d - D)^2 / alpha with D = out_depth / max(1 - final_T, 1e-10), alpha = max(1 - final_T,
+ *                         1e-10): the variance of depth along the ray in the units of depth squared, accumulated as
+ *                         written (every term >= 0); 0 where nothing contributed
+ *      median_depth[H,W]  depth (record slot 2, bit for bit) of the first contributing Gaussian, front to back, behind
+ *                         which the transmittance is <= 1/2; 0 where the transmittance never gets there (alpha < 1/2)
+ *      median_gid[H,W]    (may be NULL) that Gaussian's id, -1 if none
+ * tile_start is const here: the pass neither reads nor writes the scratch ints behind the starts (walk statistics, slot
+ * counters), so it may run between a forward and its backward; tile_start_len is validated like in the other rasterize
+ * calls (it is the same buffer).  opts: k6_split / k6_split_floor / k6_split_heads choose which long tiles are walked by
+ * four blocks, as in the forward (bit-identical either way); the other fields are not looked at. */
+int tgs_rasterize_depth_stats(const TgsCamera* cam /*[host]*/, const float* splats, const int32_t* sorted_gid,
+                              const int32_t* tile_start, int64_t tile_start_len, const int32_t* tile_order /*may be NULL*/,
+                              const float* out_depth, const float* final_T, const int32_t* stop_pos /*may be NULL*/,
+                              float* depth_var, float* median_depth, int32_t* median_gid /*may be NULL*/,
+                              const TgsRasterOpts* opts /*[host], may be NULL*/, void* stream);
+
 /* Developer switch (A/B runs, tests): k6_blocks_on 1 / 0 = K6 in 4x4-block / quadrant form,
  * k7_front_to_back 1 / 0 = K7 in the front-to-back form of TGS_VERSION 100 / back to front; -1 leaves a
  * setting as it is.  Defaults: environment TGS_K6_BLOCKS (1), TGS_K7_F2B (0), read once at first use.

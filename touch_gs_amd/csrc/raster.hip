@@ -675,6 +675,241 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
 }
 
 // ---------------------------------------------------------------------------------------------
+// K6s depth statistics: per-pixel depth variance and median depth (forward only, after K6)
+// ---------------------------------------------------------------------------------------------
+// A second walk over the lists K6 composited, in K6's launch shape (4x4-block form, long tiles split into quadrant
+// blocks by the same rule), with K6's staging, eval_s and blend_step on the same bits: every pixel includes exactly the
+// entries the forward included, with the same weights w = alpha T.  Two accumulators per pixel instead of five:
+//   V   = sum w (d - Dhat)^2, Dhat = out_depth / max(1 - final_T, 1e-10) from K6's images.  Every term is >= 0 (the
+//         moment form sum w d^2 / alpha - Dhat^2 cancels by up to 1e4 on the oracle's scenes: two digits left in fp32),
+//         and an error of Dhat enters in second order only (sum w (d - Dhat) = 0).
+//   med = the first included entry with T' = T (1 - alpha) <= 1/2.  The entry that stops a pixel has T <= 1e-4 / 0.001
+//         = 0.1 in front of it, so the crossing is always an included entry.  T only falls, so that entry is the LAST
+//         included one that finds T > 1/2 in front of it -- provided the pixel ends with T <= 1/2: one compare and one
+//         select per entry (the test against the pixel's own final T is made once, at the store).  The register holds
+//         a code: ~position once final (negative; MED_NONE = ~0x7fffffff), or -- 4x4-block form, whose rows walk
+//         different entries -- the lane's batch-relative index j >= 0 until the end of the batch (no add per entry).
+// stop_pos (optional): the walk of a tile (quadrant) ends at the deepest stop of its pixels -- no entry at or behind
+// a pixel's stop position contributes to it; the per-pixel stop itself is recomputed by blend_step either way, so the
+// outputs are bit-identical with and without it.  Nothing behind the tile starts is read or written.
+constexpr int MED_NONE = (int)0x80000000;
+template <bool MAYCLAMP>
+__device__ __forceinline__ void depth_stats_step(float s, float d, int code, float stopv, float Dhat, float& T, float& smax,
+                                                 float& V, int& med) {
+  float Tn; bool go;
+  unsigned long long okb = 0ull;
+  const float al = blend_step<MAYCLAMP, 0>(s, T, smax, Tn, go, okb, stopv);
+  const float w = al * T;
+  const float r = d - Dhat;
+  V = fmaf(w, r * r, V);
+  med = (go && T > 0.5f) ? code : med;
+  T = go ? Tn : T;
+}
+
+struct DepthStatsOut { float* var; float* med_depth; int32_t* med_gid; };
+
+// T = the transmittance the walk itself ended with (bit for bit the forward's final_T)
+__device__ __forceinline__ void depth_stats_store(const DepthStatsOut& o, size_t p, float V, float fT, float T, int med, int start,
+                                                  const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid) {
+  o.var[p] = V / fmaxf(1.f - fT, 1e-10f);
+  int gid = -1;
+  float md = 0.f;
+  if (med != MED_NONE && T <= 0.5f) {
+    gid = sorted_gid[start + ~med];
+    md = splats[(size_t)gid * TGS_SPLAT_FLOATS + 2];
+  }
+  o.med_depth[p] = md;
+  if (o.med_gid) o.med_gid[p] = gid;
+}
+
+// one 8x8 quadrant of a long tile, one pixel per lane (the counterpart of raster_fwd_quadrant)
+__device__ __forceinline__ void depth_stats_quadrant(
+    const CamK& cam, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+    const int32_t* __restrict__ tile_start, const float* __restrict__ out_depth, const float* __restrict__ final_T,
+    const int32_t* __restrict__ stop_pos, const DepthStatsOut& o, int tile, int k, float4* __restrict__ recs) {
+  const int lane = threadIdx.x;
+  const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
+  const PixConst pc = make_pix_const(lane);
+  const float pu = (k & 1) ? pc.u[1] : pc.u[0], pv = (k >> 1) ? pc.v[1] : pc.v[0];
+  const float puu = (k & 1) ? pc.uu[1] : pc.uu[0], pvv = (k >> 1) ? pc.vv[1] : pc.vv[0];
+  const float puv = k == 0 ? pc.uv[0] : (k == 1 ? pc.uv[1] : (k == 2 ? pc.uv[2] : pc.uv[3]));
+  const int px = tx * TGS_BLOCK + 8 * (k & 1) + (lane & 7);
+  const int py = ty * TGS_BLOCK + 8 * (k >> 1) + (lane >> 3);
+  const bool inb = px < cam.W && py < cam.H;
+  const size_t p = inb ? (size_t)py * cam.W + px : 0;
+  float smax = inb ? LOG2_255 : -3.0e38f;
+  const float fT = inb ? final_T[p] : 1.f;
+  const float Dhat = inb ? out_depth[p] / fmaxf(1.f - fT, 1e-10f) : 0.f;
+  float T = 1.f, V = 0.f;
+  int med = MED_NONE;
+  const int start = tile_start[tile];
+  int end = tile_start[tile + 1];
+  if (stop_pos) end = start + wave_minmax_i<true>(inb ? min(stop_pos[p], end - start) : 0);
+  for (int base = start; base < end; base += 64) {
+    if (__ballot(smax > 0.f) == 0ull) break;
+    __syncthreads();
+    unsigned my_mask = 0u;
+    if (base + lane < end) {
+      const float* r = splats + (size_t)sorted_gid[base + lane] * TGS_SPLAT_FLOATS;
+      const float4 q0 = ld4(r), q1 = ld4(r + 4), q2 = ld4(r + 8);
+      float gx, gy;
+      centre_rel(q0, q2, tx, ty, cam.pix_center, gx, gy);
+      const TileRec t = make_tile_rec(q0, q1, q2, gx, gy);
+      recs[lane * 3] = t.a; recs[lane * 3 + 1] = t.b; recs[lane * 3 + 2] = t.c;
+      my_mask = __float_as_uint(t.c.w);
+    }
+    __syncthreads();
+    unsigned long long rem = __ballot((my_mask >> k) & 1u);
+    while (rem) {
+      const int j = __builtin_ctzll(rem);
+      rem &= rem - 1;
+      const float4 qa = recs[j * 3], qb = recs[j * 3 + 1];
+      float s = fmaf(qa.y, pu, qa.x);          // eval_s for slot k
+      s = fmaf(qa.z, pv, s);
+      s = fmaf(qa.w, puu, s);
+      s = fmaf(qb.x, puv, s);
+      s = fmaf(qb.y, pvv, s);
+      depth_stats_step<true>(s, qb.z, ~(base - start + j), stop_code(base - start + j), Dhat, T, smax, V, med);
+    }
+  }
+  if (inb) depth_stats_store(o, p, V, fT, T, med, start, splats, sorted_gid);
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVES, 8))) void k_raster_depth_stats(
+    CamK cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+    const int32_t* __restrict__ tile_start, const float* __restrict__ out_depth, const float* __restrict__ final_T,
+    const int32_t* __restrict__ stop_pos, DepthStatsOut o, const int32_t* __restrict__ tile_order, SplitRule split) {
+  __shared__ float4 recs[65 * 3];                 // 64 staged Gaussians + the null record (alpha = 0)
+  int slot = blockIdx.x, part = -1;
+  if (slot >= split.n_slots) {                    // extra blocks: quadrants 1..3 of the schedule's first `heads` tiles
+    const int e = slot - split.n_slots;
+    slot = e / 3; part = 1 + (e - 3 * slot);
+  }
+  const int tile = tile_order ? tile_order[slot] : xcd_tile(slot, T_total);
+  if (tile >= T_total) return;
+  if (split.factor > 0) {
+    const bool sp = slot < split.heads && tile_is_split(tile_start[tile + 1] - tile_start[tile], tile_start[T_total], split);
+    if (part >= 0 && !sp) return;
+    if (sp) {
+      depth_stats_quadrant(cam, splats, sorted_gid, tile_start, out_depth, final_T, stop_pos, o, tile, part < 0 ? 0 : part, recs);
+      return;
+    }
+  }
+  const int lane = threadIdx.x;
+  const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
+  // lane -> pixel as in k_raster_fwd_blocks: DPP row g owns block (g & 1, g >> 1) of the quadrant
+  const int g = lane >> 4, lx = 4 * (g & 1) + (lane & 3), ly = 4 * (g >> 1) + ((lane >> 2) & 3);
+  PixConst pc;
+  pc.u[0] = (float)lx - 7.5f; pc.u[1] = pc.u[0] + 8.f;
+  pc.v[0] = (float)ly - 7.5f; pc.v[1] = pc.v[0] + 8.f;
+#pragma unroll
+  for (int i = 0; i < 2; i++) { pc.uu[i] = pc.u[i] * pc.u[i]; pc.vv[i] = pc.v[i] * pc.v[i]; }
+#pragma unroll
+  for (int k = 0; k < 4; k++) pc.uv[k] = pc.u[k & 1] * pc.v[k >> 1];
+  const int start = tile_start[tile];
+  int end = tile_start[tile + 1];
+  bool inb[4];
+  size_t pix[4];
+  float smax[4], fT[4], Dhat[4];
+  int deepest = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int px = tx * TGS_BLOCK + 8 * (k & 1) + lx, py = ty * TGS_BLOCK + 8 * (k >> 1) + ly;
+    inb[k] = (px < cam.W) && (py < cam.H);
+    pix[k] = inb[k] ? (size_t)py * cam.W + px : 0;
+    smax[k] = inb[k] ? LOG2_255 : -3.0e38f;
+    fT[k] = inb[k] ? final_T[pix[k]] : 1.f;
+    Dhat[k] = inb[k] ? out_depth[pix[k]] / fmaxf(1.f - fT[k], 1e-10f) : 0.f;
+    if (stop_pos) deepest = max(deepest, inb[k] ? min(stop_pos[pix[k]], end - start) : 0);
+  }
+  if (stop_pos) end = start + wave_minmax_i<true>(deepest);
+  float T[4] = {1.f, 1.f, 1.f, 1.f};
+  float V[4] = {0.f, 0.f, 0.f, 0.f};
+  int med[4] = {MED_NONE, MED_NONE, MED_NONE, MED_NONE};
+
+  __shared__ unsigned int lists4[16 * 16];        // 16 lists of 64 one-byte indices, padded with 64 = null
+  unsigned char* lists = reinterpret_cast<unsigned char*>(lists4);
+  if (lane == 0) {
+    recs[64 * 3] = make_float4(3.0e38f, 0.f, 0.f, 0.f);
+    recs[64 * 3 + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    recs[64 * 3 + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  int myblock[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) myblock[k] = 4 * (2 * (k >> 1) + (g >> 1)) + 2 * (k & 1) + (g & 1);
+
+  unsigned live16 = 0xffffu;
+  for (int base = start; base < end; base += 64) {
+    unsigned long long lv[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) lv[k] = __ballot(smax[k] > 0.f);
+    if ((lv[0] | lv[1] | lv[2] | lv[3]) == 0ull) break;
+    if ((((base - start) >> 6) & 3) == 0) {
+      live16 = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          live16 |= ((lv[k] >> (16 * r)) & 0xffffull) ? (1u << (4 * (2 * (k >> 1) + (r >> 1)) + 2 * (k & 1) + (r & 1))) : 0u;
+    }
+    __syncthreads();
+    unsigned my_mask = 0u;
+    float my_opac = 0.f;
+    if (base + lane < end) {
+      const float* r = splats + (size_t)sorted_gid[base + lane] * TGS_SPLAT_FLOATS;
+      const float4 q0 = ld4(r), q1 = ld4(r + 4), q2 = ld4(r + 8);
+      float gx, gy;
+      centre_rel(q0, q2, tx, ty, cam.pix_center, gx, gy);
+      const TileRec t = make_tile_rec<false>(q0, q1, q2, gx, gy);
+      recs[lane * 3] = t.a; recs[lane * 3 + 1] = t.b;      // (the colours of t.c are not read here)
+      my_mask = block_mask16(gx, gy, q1.x, q1.y, q1.z, -__log2f(q0.w)) & live16;
+      my_opac = q0.w;
+    }
+    const bool clampy = __ballot(my_opac > CLAMP_FREE_OPACITY) != 0ull;
+    reinterpret_cast<uint4*>(lists4)[lane] = make_uint4(0x40404040u, 0x40404040u, 0x40404040u, 0x40404040u);
+    __syncthreads();
+    int cnt[16];
+#pragma unroll
+    for (int b = 0; b < 16; b++) {
+      const bool in = (my_mask >> b) & 1u;
+      const unsigned long long bal = __ballot(in);
+      cnt[b] = __popcll(bal);
+      if (in) lists[b * 64 + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = (unsigned char)lane;
+    }
+    __syncthreads();
+    auto walk = [&](auto mayclamp) {
+      constexpr bool MAYCLAMP = decltype(mayclamp)::value;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int b0 = 8 * (k >> 1) + 2 * (k & 1);
+        const int n = max(max(cnt[b0], cnt[b0 + 1]), max(cnt[b0 + 4], cnt[b0 + 5]));
+        const BLK_T* mylist = reinterpret_cast<const BLK_T*>(lists4) + myblock[k] * (64 / BLK_U);
+        for (int i4 = 0; BLK_U * i4 < n; i4++) {
+          const unsigned idx4 = mylist[i4];
+#pragma unroll
+          for (int e = 0; e < BLK_U; e++) {
+            const int j = (idx4 >> (8 * e)) & 0xffu;               // 64 = null record: s = 3e38, alpha = 0
+            const float4 qa = recs[j * 3], qb = recs[j * 3 + 1];
+            depth_stats_step<MAYCLAMP>(eval_s(qa, qb, pc, k), qb.z, j, batch_stop_code(j), Dhat[k],
+                                       T[k], smax[k], V[k], med[k]);
+          }
+        }
+      }
+    };
+    if (clampy) walk(std::true_type{}); else walk(std::false_type{});
+    // batch-relative codes -> final ones (4 selects per batch, not per entry)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      smax[k] = finish_batch_stop(smax[k], base - start);
+      med[k] = med[k] >= 0 ? ~(base - start + med[k]) : med[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (inb[k]) depth_stats_store(o, pix[k], V[k], fT[k], T[k], med[k], start, splats, sorted_gid);
+}
+
+// ---------------------------------------------------------------------------------------------
 // K7 backward
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ size_t pair_index(const int32_t* __restrict__ group_base, int gid,
@@ -2342,6 +2577,32 @@ extern "C" int tgs_rasterize_fwd(const TgsCamera* cam, const float* splats,
   if (final_idx) { if (slot_ok) TGS_LAUNCH_FWD(true, true); else TGS_LAUNCH_FWD(true, false); }
   else { if (slot_ok) TGS_LAUNCH_FWD(false, true); else TGS_LAUNCH_FWD(false, false); }
 #undef TGS_LAUNCH_FWD
+  TGS_CHECK_LAUNCH();
+  return TGS_OK;
+}
+
+extern "C" int tgs_rasterize_depth_stats(const TgsCamera* cam, const float* splats, const int32_t* sorted_gid,
+                                         const int32_t* tile_start, int64_t tile_start_len, const int32_t* tile_order,
+                                         const float* out_depth, const float* final_T, const int32_t* stop_pos,
+                                         float* depth_var, float* median_depth, int32_t* median_gid,
+                                         const TgsRasterOpts* opts, void* stream) {
+  TGS_CHECK_ARG(camera_ok(cam), "bad camera");
+  TGS_CHECK_ARG(cam->W <= 255 * TGS_BLOCK && cam->H <= 255 * TGS_BLOCK, "image sides are limited to 4080 px (255 tiles)");
+  TGS_CHECK_ARG(splats && sorted_gid && tile_start && out_depth && final_T && depth_var && median_depth, "null pointer");
+  const CamK k = make_camk(cam);
+  const int T = k.TW * k.TH;
+  TGS_CHECK_ARG(tile_start_len >= (int64_t)T + 1 + TGS_TILE_START_SCRATCH,
+                "tile_start buffer shorter than tgs_tile_start_len(W, H) (the buffer of the forward these lists were composited with)");
+  const int grid = TGS_XCDS * tgs_xcd_slots(T);
+  // K6's launch shape: long tiles in four quadrant blocks, by the rule (and the per-call fields) of the forward
+  SplitRule sr;
+  sr.factor = tile_order ? opt_or(opts, &TgsRasterOpts::k6_split, g_k6_split) : 0;
+  sr.n_slots = grid;
+  sr.heads = sr.factor > 0 ? min(grid, opt_or(opts, &TgsRasterOpts::k6_split_heads, g_k6_heads)) : 0;
+  sr.floor = max(64, opt_or(opts, &TgsRasterOpts::k6_split_floor, g_k6_floor));
+  DepthStatsOut o{depth_var, median_depth, median_gid};
+  hipLaunchKernelGGL(k_raster_depth_stats, dim3(grid + 3 * sr.heads), dim3(64), 0, (hipStream_t)stream, k, T, splats,
+                     sorted_gid, tile_start, out_depth, final_T, stop_pos, o, tile_order, sr);
   TGS_CHECK_LAUNCH();
   return TGS_OK;
 }

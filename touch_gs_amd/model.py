@@ -201,19 +201,36 @@ class DepthGaussianSplattingModel:
             return min(c.sh_degree, max_deg)
         return min((self.step if step is None else step) // c.sh_degree_interval, c.sh_degree, max_deg)
 
-    def get_outputs(self, cam: Camera, sh_degree: Optional[int] = None) -> Dict[str, torch.Tensor]:
-        """Camera -> {rgb, depth, accumulation} (differentiable; autograd path)."""
+    def get_outputs(self, cam: Camera, sh_degree: Optional[int] = None, depth_stats: bool = False) -> Dict[str, torch.Tensor]:
+        """Camera -> {rgb, depth, accumulation} (differentiable; autograd path).
+
+        ``depth_stats=True`` adds ``median_depth`` [H,W,1] (depth of the Gaussian behind which the transmittance first is
+        <= 1/2; 0 where alpha < 1/2), ``depth_var`` / ``depth_std`` [H,W,1] (spread of depth along the ray around the
+        expected depth, scene units squared / scene units) and ``median_gid`` int32 [H,W] (-1 = none): a second walk
+        over the frame's lists (ops.rasterize_depth_stats), detached -- no gradients flow through them.  The other
+        keys and their values are those of the default call."""
         p = self.params
         deg = self.active_sh_degree() if sh_degree is None else sh_degree
         # the autograd / eval path has no replay logic: it always bins with a synchronous budget (a
         # sync-free training budget would turn an eval view that needs more pairs into background)
         budget = self.budget if self.budget.sync else self._sync_budget
-        rgb, depth_acc, alpha, radii = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
-                                                  self.tuned(cam, keep=False), deg, budget=budget,
-                                                  opts=self.tuning.raster_opts())
+        stats = ()
+        if depth_stats:
+            rgb, depth_acc, alpha, radii, *stats = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
+                                                              self.tuned(cam, keep=False), deg, budget=budget,
+                                                              opts=self.tuning.raster_opts(), depth_stats=True)
+        else:
+            rgb, depth_acc, alpha, radii = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
+                                                      self.tuned(cam, keep=False), deg, budget=budget,
+                                                      opts=self.tuning.raster_opts())
         depth = depth_acc / torch.clamp(alpha, min=1e-10)
-        return dict(rgb=rgb, depth=depth[..., None], accumulation=alpha[..., None],
-                    depth_acc=depth_acc, alpha=alpha, radii=radii)
+        out = dict(rgb=rgb, depth=depth[..., None], accumulation=alpha[..., None],
+                   depth_acc=depth_acc, alpha=alpha, radii=radii)
+        if depth_stats:
+            var, med, gid = stats
+            out.update(median_depth=med[..., None], depth_var=var[..., None], depth_std=torch.sqrt(var)[..., None],
+                       median_gid=gid)
+        return out
 
     def depth_loss(self, depth_acc, alpha, view: View) -> torch.Tensor:
         """mean over valid (D_gt > 0) of (D_hat - D_gt)^2 [ / (uw * U + eps) ]."""
@@ -272,6 +289,19 @@ class DepthGaussianSplattingModel:
                 metrics["gt_object_depth_mse"] = float(((d - view.gt_depth)[obj] ** 2).mean()) if obj.any() else 0.0
         images = {"img": torch.cat([view.rgb, outputs["rgb"]], dim=1),
                   "depth": outputs["depth"], "accumulation": outputs["accumulation"]}
+        if "median_depth" in outputs:   # get_outputs(depth_stats=True): the same three errors for the median depth
+            # same masks as the expected-depth keys; a pixel without a median (alpha < 1/2) counts with its expected depth
+            dm = torch.where(outputs["median_gid"] >= 0, outputs["median_depth"][..., 0], outputs["depth"][..., 0])
+            mse_of = lambda ref, m: float(((dm - ref)[m] ** 2).mean()) if m.any() else 0.0
+            if view.depth is not None:
+                metrics["median_depth_mse"] = mse_of(view.depth, view.depth > 0)
+            if view.gt_depth is not None:
+                valid = view.gt_depth > 0
+                metrics["gt_depth_mse_median"] = mse_of(view.gt_depth, valid)
+                if view.object_mask is not None:
+                    metrics["gt_object_depth_mse_median"] = mse_of(view.gt_depth, valid & view.object_mask)
+            images["median_depth"] = outputs["median_depth"]
+            images["depth_std"] = outputs["depth_std"]
         return metrics, images
 
     # -- fused train step ---------------------------------------------------------------------

@@ -165,6 +165,9 @@ class AutogradGaussians:
         # resolution_schedule) of the camera's resolution; evaluation always at full resolution
         self.num_downscales = int(getattr(config, "num_downscales", 0) or 0)
         self.resolution_schedule = int(getattr(config, "resolution_schedule", 250) or 0)
+        # config field ``output_depth_stats`` (default off): every render also carries median_depth / depth_var /
+        # depth_std / median_gid (ops.rasterize_depth_stats: a second, forward-only walk; no gradients through them)
+        self.output_depth_stats = bool(getattr(config, "output_depth_stats", False))
         self.training = True
         self.step = 0
         self.track_xy_grad = False      # set by ParamGroupRefiner: render() then keeps the screen-space gradient
@@ -197,14 +200,24 @@ class AutogradGaussians:
         if self.track_xy_grad and torch.is_grad_enabled():
             # INRIA `means2D.grad` convention: a zero [N,2] leaf that receives the screen-space mean gradient
             xy = torch.zeros(p["xyz"].shape[0], 2, device=p["xyz"].device, requires_grad=True)
-        rgb, depth_acc, alpha, radii = ops.render(p["xyz"], p["scaling"], p["rotation"], p["opacity"], sh, cam,
-                                                  self.active_sh_degree() if sh_degree is None else sh_degree,
-                                                  means2d=xy, budget=self.core._sync_budget)
+        deg = self.active_sh_degree() if sh_degree is None else sh_degree
+        stats = ()
+        if self.output_depth_stats:
+            rgb, depth_acc, alpha, radii, *stats = ops.render(p["xyz"], p["scaling"], p["rotation"], p["opacity"], sh, cam, deg,
+                                                              means2d=xy, budget=self.core._sync_budget, depth_stats=True)
+        else:
+            rgb, depth_acc, alpha, radii = ops.render(p["xyz"], p["scaling"], p["rotation"], p["opacity"], sh, cam, deg,
+                                                      means2d=xy, budget=self.core._sync_budget)
         if xy is not None:
             self.last_xy, self.last_radii, self.last_wh = xy, radii, (cam.W, cam.H)
         depth = depth_acc / torch.clamp(alpha, min=1e-10)
-        return dict(rgb=rgb, depth=depth[..., None], accumulation=alpha[..., None], depth_acc=depth_acc, alpha=alpha,
-                    radii=radii)
+        out = dict(rgb=rgb, depth=depth[..., None], accumulation=alpha[..., None], depth_acc=depth_acc, alpha=alpha,
+                   radii=radii)
+        if self.output_depth_stats:
+            var, med, gid = stats
+            out.update(median_depth=med[..., None], depth_var=var[..., None], depth_std=torch.sqrt(var)[..., None],
+                       median_gid=gid)
+        return out
 
     @staticmethod
     def view_from_batch(batch, like):
@@ -438,6 +451,9 @@ if available:  # pragma: no cover
         # densify.py: cull Gaussians unseen for a whole refinement window.  nerfstudio's datamanager draws the views at
         # random per epoch, so the window only counts as complete from refine_every >= 2 num_train_data - 1
         cull_unseen: bool = False
+        # get_outputs also carries median_depth / depth_var / depth_std [H,W,1] and median_gid [H,W] (a second compositing
+        # walk per render, no gradients through them; the eval metrics then gain median_depth_mse and its gt_ variants)
+        output_depth_stats: bool = False
 
     class DepthGSNerfstudioModel(Model):
         """Thin shell: nerfstudio Model API -> AutogradGaussians / ParamGroupRefiner (above).  Parameters

@@ -380,6 +380,32 @@ def rasterize_fwd(cam: Camera, splats, sorted_gid, tile_start, want_idx: bool = 
     return rgb, depth, fT, fidx
 
 
+def rasterize_depth_stats(cam: Camera, splats, sorted_gid, tile_start, depth_acc, final_T, want_gid: bool = False, opts=None):
+    """K6s -> (depth_var [H,W], median_depth [H,W], median_gid int32 [H,W] or None).  (tgs_rasterize_depth_stats)
+
+    A second, forward-only walk over the lists ``rasterize_fwd`` composited; ``depth_acc`` / ``final_T`` are that call's
+    outputs.  ``depth_var`` = sum w (d - D)^2 / alpha around the expected depth D = depth_acc / alpha; ``median_depth`` =
+    depth of the Gaussian behind which the transmittance first is <= 1/2 (0 where alpha < 1/2, ``median_gid`` -1).  Uses
+    ``final_T.stop_pos`` when the forward left it (it only shortens the walk).  No gradients flow through the outputs."""
+    lib = _lib.load()
+    dev = splats.device
+    H, W = cam.H, cam.W
+    _check_tile_start(tile_start, cam.num_tiles)
+    depth_acc, fT = _f32c(depth_acc.detach()), _f32c(final_T.detach())
+    if tuple(depth_acc.shape) != (H, W) or tuple(fT.shape) != (H, W):
+        raise ValueError(f"depth_acc / final_T must be [{H},{W}]")
+    stop = getattr(final_T, "stop_pos", None)
+    var = torch.empty(H, W, dtype=torch.float32, device=dev)
+    med = torch.empty(H, W, dtype=torch.float32, device=dev)
+    gid = torch.empty(H, W, dtype=torch.int32, device=dev) if want_gid else None
+    cs = cam.c_struct()
+    check(lib.tgs_rasterize_depth_stats(C.byref(cs), ptr(splats), ptr(sorted_gid), ptr(tile_start), _tile_start_len(tile_start),
+                                        ptr(getattr(tile_start, "tile_order", None)), ptr(depth_acc), ptr(fT), ptr(stop),
+                                        ptr(var), ptr(med), ptr(gid), C.byref(opts) if opts is not None else None,
+                                        _stream()), "tgs_rasterize_depth_stats")
+    return var, med, gid
+
+
 def rasterize_bwd(cam: Camera, splats, group_base, sorted_gid, tile_start, rgb, depth, fT,
                   v_rgb=None, v_depth=None, v_alpha=None, loss: Optional[dict] = None,
                   want_tile_loss: bool = False, stop_pos=None, partials=None, opts=None):
@@ -613,7 +639,8 @@ def dp_agree_overflow(world: int, N: int, v_color_all, status_out, sticky=None):
 # ------------------------------------------------------------------------------------------------
 class _Render(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd=True, opts=None):
+    def forward(ctx, means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd=True, opts=None,
+                depth_stats=False):
         means, log_scales, quats, opac_logit, sh = map(_f32c, (means, log_scales, quats, opac_logit, sh))
         splats, radii, group_base, tile_start, sorted_gid, _ = project_bin_sort(
             cam, means, log_scales, quats, opac_logit, sh, sh_deg, budget, want_radii=True)
@@ -626,11 +653,15 @@ class _Render(torch.autograd.Function):
             ctx.save_for_backward(means, log_scales, quats, opac_logit, sh, splats, group_base,
                                   tile_start, sorted_gid, rgb, depth, fT, fT.stop_pos)
         alpha = 1.0 - fT
+        if depth_stats:     # the second walk needs this frame's lists, which do not leave this function
+            var, med, gid = rasterize_depth_stats(cam, splats, sorted_gid, tile_start, depth, fT, want_gid=True, opts=opts)
+            ctx.mark_non_differentiable(radii, var, med, gid)
+            return rgb, depth, alpha, radii, var, med, gid
         ctx.mark_non_differentiable(radii)
         return rgb, depth, alpha, radii
 
     @staticmethod
-    def backward(ctx, v_rgb, v_depth, v_alpha, _v_radii):
+    def backward(ctx, v_rgb, v_depth, v_alpha, _v_radii, *_v_stats):
         (means, log_scales, quats, opac_logit, sh, splats, group_base, tile_start, sorted_gid,
          rgb, depth, fT, stop) = ctx.saved_tensors
         cam = ctx.cam
@@ -639,11 +670,12 @@ class _Render(torch.autograd.Function):
         v_means, v_ls, v_q, v_ol, v_sh, v_xy = project_bwd(
             cam, means, log_scales, quats, opac_logit, sh, ctx.sh_deg, splats, group_base, partials,
             want_v_xy=ctx.want_xy)
-        return v_means, v_ls, v_q, v_ol, v_sh, v_xy, None, None, None, None, None
+        return v_means, v_ls, v_q, v_ol, v_sh, v_xy, None, None, None, None, None, None
 
 
 def render(means, log_scales, quats, opac_logit, sh, cam: Camera, sh_deg: int,
-           means2d: Optional[torch.Tensor] = None, budget: Optional[IntersectBudget] = None, opts=None):
+           means2d: Optional[torch.Tensor] = None, budget: Optional[IntersectBudget] = None, opts=None,
+           depth_stats: bool = False):
     """Fused differentiable render of RGB + depth + alpha in one compositing pass.
 
     Parameters are the raw (pre-activation) Gaussian parameters of SURVEY App. B.0.
@@ -652,10 +684,15 @@ def render(means, log_scales, quats, opac_logit, sh, cam: Camera, sh_deg: int,
     Returns (rgb [H,W,3] incl. background, depth_acc [H,W] = sum w*z, alpha [H,W], radii [N]).
     Expected depth is ``depth_acc / alpha`` (consumer side, as Splatfacto does).
     ``opts`` = ``raster_opts(...)`` for the forward of this call only.
+    ``depth_stats=True`` appends (depth_var [H,W], median_depth [H,W], median_gid int32 [H,W]) of
+    :func:`rasterize_depth_stats` to the tuple: a second walk over the same lists.  The three are detached -- there is
+    no autograd through the variance or the median; the first four entries are what the default call returns.
     """
     need_bwd = torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                for t in (means, log_scales, quats, opac_logit, sh, means2d))
-    return _Render.apply(means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd, opts)
+    if not depth_stats:
+        return _Render.apply(means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd, opts)
+    return _Render.apply(means, log_scales, quats, opac_logit, sh, means2d, cam, sh_deg, budget, need_bwd, opts, True)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -22,9 +22,10 @@ import os
 import torch
 
 
-def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda") -> dict:
+def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False) -> dict:
     """Rebuild the model of one training run from its config.json + newest checkpoint and evaluate
-    it on the run's eval split."""
+    it on the run's eval split.  ``depth_stats``: the results gain median_depth_mse / gt_depth_mse_median /
+    gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views)."""
     from .dataset import Scene
     from .model import DepthGaussianSplattingModel, ModelConfig
     from .optim import GaussianParams
@@ -43,19 +44,19 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda") -> dic
         from .scene import make_view
         N, W, H = cfg["synthetic"]
         views = [make_view(N, W, H, cfg["sh_degree"], 1235, device, view=7, n_views=8)]
-        names = None
+        names, scale = None, 1.0
     else:
         scene = Scene(cfg["data"], cfg["train_split_fraction"], device)
         idx = list(scene.i_eval) or list(scene.i_train)[:1]
-        views, names = [scene.views[i] for i in idx], [scene.names[i] for i in idx]
-    results = evaluate(model, views)
+        views, names, scale = [scene.views[i] for i in idx], [scene.names[i] for i in idx], scene.scale
+    results = evaluate(model, views, depth_stats=depth_stats)
     results.setdefault("lpips", float("nan"))   # get_results.py:38 indexes it unconditionally
     os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
     with open(out_json, "w") as f:
         json.dump({"experiment_name": os.path.basename(os.path.dirname(os.path.dirname(run_dir))),
                    "method_name": "depth-gaussian-splatting", "checkpoint": ckpts[-1], "results": results}, f, indent=2)
     if render_dir:
-        render_views(model, views, render_dir, names)
+        render_views(model, views, render_dir, names, depth_stats=depth_stats, dataparser_scale=scale)
     return results
 
 
@@ -66,6 +67,9 @@ def main(argv=None):
     ap.add_argument("--exp_name", required=True)
     ap.add_argument("--past_n_trials", type=int, required=True)
     ap.add_argument("--no_render", action="store_true")
+    ap.add_argument("--depth-stats", "--depth_stats", dest="depth_stats", action="store_true",
+                    help="also evaluate the median depth and dump median_depth/ + uncertainty/ (rendered depth variance, "
+                         "uint16 like the input uncertainty maps)")
     a = ap.parse_args(argv)
     full_exp_dir = os.path.join(a.output_dir, a.exp_name)
     os.makedirs(full_exp_dir, exist_ok=True)
@@ -75,7 +79,7 @@ def main(argv=None):
         if not os.path.exists(os.path.join(run_dir, "config.json")):
             continue
         out_json = os.path.join(full_exp_dir, f"{a.exp_name}_{len(done) + 1}.json")
-        res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders")
+        res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders", depth_stats=a.depth_stats)
         print(out_json, json.dumps(res))
         done.append(out_json)
         if len(done) == a.past_n_trials:

@@ -78,31 +78,56 @@ def init_params(n: int, K: int, device, seed_points=None, extent: float = 1.0, s
 
 
 @torch.no_grad()
-def evaluate(model: DepthGaussianSplattingModel, views) -> dict:
+def evaluate(model: DepthGaussianSplattingModel, views, depth_stats: bool = False) -> dict:
+    """Mean of the eval metrics over ``views``.  ``depth_stats``: also median_depth_mse / gt_depth_mse_median /
+    gt_object_depth_mse_median (the median depth under the masks of the expected-depth keys, whose values do not change)."""
     acc = {}
     for v in views:
-        out = model.get_outputs(v.cam, sh_degree=model.active_sh_degree())
+        out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True) if depth_stats else
+               model.get_outputs(v.cam, sh_degree=model.active_sh_degree()))
         m, _ = model.get_image_metrics_and_images(out, v)
         for k, x in m.items():
             acc.setdefault(k, []).append(x)
     return {k: float(sum(x) / len(x)) for k, x in acc.items()}
 
 
-def render_views(model: DepthGaussianSplattingModel, views, out_dir: str, names=None) -> None:
+def uncertainty_png(depth_var, dataparser_scale: float = 1.0):
+    """Rendered depth variance [H,W] (scene units squared) -> the uint16 image of the pipeline's uncertainty maps
+    (utils/fuse_touch_vision.py:372-376): back to m^2 with the dataparser scale squared, clipped to [0, 10], x 1000,
+    truncated -- ``plumbing.to_uint16_mm``, so the file loads through the reader of the input maps (dataset.py)."""
+    import numpy as np
+    from .plumbing import to_uint16_mm
+    var_m2 = depth_var.detach().double().cpu().numpy() / (float(dataparser_scale) ** 2)
+    return to_uint16_mm(np.clip(var_m2, 0.0, 10.0))
+
+
+def render_views(model: DepthGaussianSplattingModel, views, out_dir: str, names=None, depth_stats: bool = False,
+                 dataparser_scale: float = 1.0) -> None:
     """The build's counterpart of ``ns-render dataset`` (reference experiment_utils/run_eval.py:48):
     ``<out_dir>/rgb/<name>.png`` (8-bit) and ``<out_dir>/depth/<name>.png`` (uint16 millimetres, the
-    convention of the dataset's own depth maps: utils/fuse_touch_vision.py:372-376)."""
+    convention of the dataset's own depth maps: utils/fuse_touch_vision.py:372-376).
+    ``depth_stats``: also ``median_depth/<name>.png`` (like depth/) and ``uncertainty/<name>.png``, the rendered depth
+    variance in the format of the input uncertainty maps (``uncertainty_png``; ``dataparser_scale`` = Scene.scale)."""
     from PIL import Image
     from .plumbing import write_png16
     os.makedirs(os.path.join(out_dir, "rgb"), exist_ok=True)
     os.makedirs(os.path.join(out_dir, "depth"), exist_ok=True)
+    if depth_stats:
+        os.makedirs(os.path.join(out_dir, "median_depth"), exist_ok=True)
+        os.makedirs(os.path.join(out_dir, "uncertainty"), exist_ok=True)
     for i, v in enumerate(views):
-        out = model.get_outputs(v.cam, sh_degree=model.active_sh_degree())
+        out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True) if depth_stats else
+               model.get_outputs(v.cam, sh_degree=model.active_sh_degree()))
         name = os.path.splitext(os.path.basename(names[i]))[0] if names else f"{i:05d}"
         rgb = (out["rgb"].clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
         Image.fromarray(rgb).save(os.path.join(out_dir, "rgb", name + ".png"))
         mm = (out["depth"].reshape(v.cam.H, v.cam.W) * 1000.0).clamp(0, 65535).round().to(torch.int32).cpu().numpy()
         write_png16(os.path.join(out_dir, "depth", name + ".png"), mm.astype("uint16"))
+        if depth_stats:
+            mm = (out["median_depth"].reshape(v.cam.H, v.cam.W) * 1000.0).clamp(0, 65535).round().to(torch.int32).cpu().numpy()
+            write_png16(os.path.join(out_dir, "median_depth", name + ".png"), mm.astype("uint16"))
+            write_png16(os.path.join(out_dir, "uncertainty", name + ".png"),
+                        uncertainty_png(out["depth_var"].reshape(v.cam.H, v.cam.W), dataparser_scale))
 
 
 def main(argv=None):
@@ -141,6 +166,10 @@ def main(argv=None):
                     help="read the intersection count back every step instead of the sync-free speculative budget")
     ap.add_argument("--render-output", type=str, default=None,
                     help="also dump the eval views' renders (rgb/ + 16-bit mm depth/), like ns-render dataset")
+    ap.add_argument("--eval-depth-stats", action="store_true",
+                    help="final evaluation also renders median depth and per-pixel depth variance: eval.json gains "
+                         "median_depth_mse (+ gt_depth_mse_median / gt_object_depth_mse_median), --render-output gains "
+                         "median_depth/ and uncertainty/ (the format of the input uncertainty maps)")
     ap.add_argument("--output-dir", type=str, default="outputs")
     ap.add_argument("--load-checkpoint", type=str, default=None)
     ap.add_argument("--seed", type=int, default=0)
@@ -261,7 +290,7 @@ def main(argv=None):
         print(f"gaussians {model.params.N}  refinements {n_refines}  speculative replays "
               f"{getattr(model, 'speculative_replays', 0)}", flush=True)
     if dp.rank == 0:
-        results = evaluate(model, eval_views)
+        results = evaluate(model, eval_views, depth_stats=args.eval_depth_stats)
         # the reference's aggregator indexes results['lpips'] unconditionally
         # (experiment_utils/get_results.py:38); LPIPS needs pretrained network weights that cannot be
         # fetched here, so the key is present and NaN rather than absent
@@ -272,7 +301,8 @@ def main(argv=None):
         print(json.dumps(results))
         if args.render_output:
             render_views(model, eval_views, args.render_output,
-                         None if args.synthetic is not None else [scene.names[i] for i in i_eval] if i_eval else None)
+                         None if args.synthetic is not None else [scene.names[i] for i in i_eval] if i_eval else None,
+                         depth_stats=args.eval_depth_stats, dataparser_scale=1.0 if args.synthetic is not None else scene.scale)
     dp.barrier()
     if dp.peer is not None:
         dp.peer.close()
