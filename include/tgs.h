@@ -564,6 +564,24 @@ int tgs_ssim_fwd_bwd_rows(int W, int H, const float* img, const float* gt, float
                           float* block_partials, int n_partials, float* v_img, float* scratch,
                           int y0, int y1, int count_y0, int count_y1, void* stream);
 
+/* Scale-invariant monocular depth loss  L = weight * (1 - rho)  (an ADDITION within TGS_VERSION 320: no struct and no earlier
+ *     signature changes; csrc/depthcorr.hip).  rho = the Pearson correlation, over the VALID pixels, of the expected depth
+ *     x = out_depth / alpha, alpha = max(1 - final_T, 1e-10)  (out_depth, final_T: tgs_rasterize_fwd's outputs) and a raw
+ *     monocular depth map y = mono of any positive scale and any shift.  A pixel is valid iff mono > 0 and
+ *     (1.0f - final_T) >= alpha_min, compared in fp32; alpha_min in (0, 1].  Over the valid pixels: n = count, mx, my = means,
+ *     vx, vy, c = centred second moments / n, rho = c / sqrt(vx vy), beta = c / vx and
+ *         g_i = -weight * d rho / d x_i = -weight / (n sqrt(vx vy)) * ((y_i - my) - beta (x_i - mx)).
+ * out: stats[8] = {n, mx, my, vx, vy, c, rho, weight * (1 - rho)};
+ *      v_depth[H,W] = g / alpha and v_alpha[H,W] = -g x / alpha (the gradient with respect to 1 - final_T): the upstream images
+ *      tgs_rasterize_bwd takes, which adds its own fused terms on top.  0 on invalid pixels; every pixel is written.  Either
+ *      may be NULL; both NULL = forward only (two launches instead of three).
+ * tmp: tile_moments[tgs_num_tiles * 8] floats.  stats and tile_moments are 16-byte aligned.
+ * A DEGENERATE frame -- n < 2, or vx vy (of the fp32 values in stats) not > 0 or not finite -- has rho = 0, loss 0 and all
+ * gradients 0; stats[0..5] are still written, nothing is NaN.  No float atomics: the same inputs give the same bits. */
+int tgs_depth_corr_fwd_bwd(int W, int H, const float* out_depth, const float* final_T, const float* mono,
+                           float alpha_min, float weight, float* tile_moments, float* stats,
+                           float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

@@ -37,6 +37,11 @@ IS_REAL_WORLD environment variable) every view also carries the sensor's depth
 ``realsense_depths/<n>.png`` (the output of the pipeline's first step) as ground truth and the
 touched region ``touch_depth/<n>.png > 0`` as object mask.  The fork that computes the two numbers
 is absent; this definition (MSE over measured pixels / over measured object pixels) is the build's.
+
+Monocular depth: ``mono_depth_dir`` (e.g. ``zoe_depth``, the pipeline's raw ZoeDepth output) gives every view whose
+``<root>/<dir>/<image stem>.png`` (uint16) or ``.npy`` exists a ``View.mono_depth``, resized to the image like the
+sensor's depth.  No unit conversion and no dataparser scale: the term that reads it (ModelConfig.mono_depth_mult) is
+invariant to the map's scale and shift.
 """
 from __future__ import annotations
 
@@ -70,8 +75,10 @@ class Scene:
     def __init__(self, root: str, train_split_fraction: float = 0.9, device="cuda", scale_poses: bool = True,
                  depth_unit_scale_factor: float = 1e-3, real_world: Optional[bool] = None,
                  gt_depth_dir: str = "realsense_depths", object_mask_dir: str = "touch_depth",
-                 uncertainty_scaling: str = "linear", uncertainty_floor: float = 0.0):
+                 uncertainty_scaling: str = "linear", uncertainty_floor: float = 0.0,
+                 mono_depth_dir: Optional[str] = None):
         self.root = root
+        self.mono_depth_dir = mono_depth_dir
         if uncertainty_scaling not in UNCERTAINTY_SCALINGS:
             raise ValueError(f"uncertainty_scaling must be one of {UNCERTAINTY_SCALINGS}")
         self.uncertainty_scaling = uncertainty_scaling
@@ -121,6 +128,8 @@ class Scene:
                         m = read_png16(m_path) > 0
                         if m.shape == (H, W):
                             view.object_mask = torch.from_numpy(m).to(device)
+            if mono_depth_dir:
+                view.mono_depth = self._read_mono(os.path.splitext(os.path.basename(fr["file_path"]))[0], H, W, device)
             self.views.append(view)
         names = [fr["file_path"] for fr in frames]
         self.names = names
@@ -128,10 +137,26 @@ class Scene:
         self._centre = np.stack([np.array(fr["transform_matrix"], dtype=np.float64)[:3, 3] for fr in frames]).mean(0) \
             if scale_poses else np.zeros(3)
 
+    def _read_mono(self, stem: str, H: int, W: int, device) -> Optional[torch.Tensor]:
+        base = os.path.join(self.root, self.mono_depth_dir, stem)
+        if os.path.exists(base + ".png"):
+            m = read_png16(base + ".png").astype(np.float32)
+        elif os.path.exists(base + ".npy"):
+            m = np.load(base + ".npy").astype(np.float32)
+            if m.ndim != 2:
+                raise ValueError(f"{base}.npy: expected a [H,W] map, got shape {m.shape}")
+        else:
+            return None
+        if m.shape != (H, W):
+            from .prepare import resize_bilinear
+            m = resize_bilinear(m, H, W).astype(np.float32)
+        return torch.from_numpy(np.ascontiguousarray(m)).to(device)
+
     def describe(self) -> dict:
         """What the trainer records in config.json about the units of the supervision maps."""
         return dict(dataparser_scale=self.scale, depth_unit_scale_factor=self.depth_unit_scale_factor,
                     uncertainty_scaling=self.uncertainty_scaling, uncertainty_floor=self.uncertainty_floor,
+                    mono_depth_dir=self.mono_depth_dir, mono_depth_views=sum(v.mono_depth is not None for v in self.views),
                     uncertainty_factor=uncertainty_factor(self.uncertainty_scaling, self.depth_unit_scale_factor,
                                                           self.scale))
 

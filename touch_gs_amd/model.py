@@ -47,6 +47,11 @@ class ModelConfig:
     depth_loss_type: str = "DEPTH_UNCERTAINTY_WEIGHTED_LOSS"
     uncertainty_weight: float = 1.0
     depth_eps: float = 1e-6
+    # scale-invariant monocular depth term  mono_depth_mult * (1 - rho(D_hat, View.mono_depth))  (ops.depth_corr_fwd_bwd):
+    # Pearson correlation over the pixels with a map value and alpha >= mono_depth_alpha_min -- the expected depth of a
+    # near-empty pixel is not a depth, and one such outlier wrecks a correlation.  0 = off: no launch, nothing changes
+    mono_depth_mult: float = 0.0
+    mono_depth_alpha_min: float = 0.5
     sh_degree_interval: int = 1000
     # Splatfacto's coarse-to-fine schedule (num_downscales 2, resolution_schedule 250): training
     # starts on images downscaled by 2^num_downscales and doubles the resolution every resolution_schedule steps.
@@ -125,6 +130,9 @@ class View:
     # (experiment_utils/get_results.py:47-51)
     gt_depth: Optional[torch.Tensor] = None     # [H,W], 0 = no measurement
     object_mask: Optional[torch.Tensor] = None  # [H,W] bool
+    # raw monocular depth (e.g. ZoeDepth), 0 = no value, any positive units: supervises through the correlation term
+    # (ModelConfig.mono_depth_mult), which is invariant to its scale and shift -- no alignment to a depth sensor needed
+    mono_depth: Optional[torch.Tensor] = None   # [H,W]
 
     def valid_count(self) -> int:
         if self.n_valid_depth is None:
@@ -134,7 +142,7 @@ class View:
     def downscaled(self, d: int) -> "View":
         """This view at 1/d of its resolution (cached): the colour image resized bilinearly to (H // d, W // d) --
         what Splatfacto's ``_downscale_if_required`` does (torchvision resize of a tensor, no antialiasing) --
-        depth and uncertainty by nearest neighbour, so that 0 stays "unsupervised" and no depth is invented across
+        depth, uncertainty and mono_depth by nearest neighbour, so that 0 stays "unsupervised" and no depth is invented across
         an object boundary; camera as ``Camera.downscaled``."""
         if d <= 1:
             return self
@@ -146,7 +154,7 @@ class View:
                                 antialias=False)[0].permute(1, 2, 0).contiguous()
             near = lambda t: None if t is None else F.interpolate(t[None, None].float(), size=(H, W), mode="nearest")[0, 0].to(t.dtype).contiguous()
             cache[d] = View(cam=self.cam.downscaled(d), rgb=rgb, depth=near(self.depth), uncertainty=near(self.uncertainty),
-                            gt_depth=near(self.gt_depth), object_mask=near(self.object_mask))
+                            gt_depth=near(self.gt_depth), object_mask=near(self.object_mask), mono_depth=near(self.mono_depth))
         return cache[d]
 
 
@@ -255,7 +263,13 @@ class DepthGaussianSplattingModel:
             loss["main_loss"] = loss["main_loss"] + c.ssim_lambda * (1 - _SSIM.apply(outputs["rgb"], view.rgb))
         if c.depth_loss_mult > 0 and view.depth is not None:
             loss["depth_loss"] = c.depth_loss_mult * self.depth_loss(outputs["depth_acc"], outputs["alpha"], view)
+        if self.mono_depth_active(view):
+            rho = ops.depth_correlation(outputs["depth_acc"], outputs["alpha"], view.mono_depth, c.mono_depth_alpha_min)
+            loss["mono_depth_loss"] = c.mono_depth_mult * (1 - rho)
         return loss
+
+    def mono_depth_active(self, view: View) -> bool:
+        return self.config.mono_depth_mult > 0 and view.mono_depth is not None
 
     @torch.no_grad()
     def get_metrics_dict(self, outputs, view: View) -> Dict[str, torch.Tensor]:
@@ -333,7 +347,11 @@ class DepthGaussianSplattingModel:
         guard = None if self.budget.sync else status   # overflowed frame => optimizer kernels are no-ops
         rgb, depth_acc, fT, fidx = ops.rasterize_fwd(cam, splats, sorted_gid, tile_start, opts=self.tuning.raster_opts())
         v_img, ssim_sum = None, None
-        if (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles
+        mono_stats = v_depth = v_alpha = None
+        if self.mono_depth_active(view):   # image-space term beside K7, which adds its fused terms on top of the two images
+            mono_stats, v_depth, v_alpha = ops.depth_corr_fwd_bwd(depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min,
+                                                                  weight=c.mono_depth_mult)
+        if (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles and mono_stats is None
                 and not torch.cuda.is_current_stream_capturing()):
             if getattr(self, "_side_stream", None) is None:
                 self._side_stream = torch.cuda.Stream(device=rgb.device)
@@ -344,7 +362,7 @@ class DepthGaussianSplattingModel:
             if c.ssim_lambda > 0:
                 ssim_sum, v_img = ops.ssim_fwd_bwd(rgb, view.rgb, weight=-c.ssim_lambda / (3 * H * W), reduce=False)
             partials, tile_loss = ops.rasterize_bwd(cam, splats, group_base, sorted_gid, tile_start, rgb,
-                                                    depth_acc, fT, v_rgb=v_img,
+                                                    depth_acc, fT, v_rgb=v_img, v_depth=v_depth, v_alpha=v_alpha,
                                                     loss=self.loss_spec(view), want_tile_loss=True)
         if fuse_adam:
             v_xy = self.optimizer.backward_and_step(cam, deg, splats, group_base, partials, want_v_xy,
@@ -370,16 +388,25 @@ class DepthGaussianSplattingModel:
                                    group_base, partials, out=p.grad_views(), want_v_xy=want_v_xy, guard=guard)[5]
         self.last = dict(rgb=rgb, depth_acc=depth_acc, final_T=fT, splats=splats, v_xy=v_xy, radii=radii,
                          tile_loss=tile_loss, ssim_sum=ssim_sum, status=status, guard=guard, view=view)
+        if mono_stats is not None:
+            self.last["mono_stats"] = mono_stats
         return tile_loss, ssim_sum
 
-    def loss_from(self, tile_loss, ssim_sum, view: View) -> Dict[str, torch.Tensor]:
+    def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None) -> Dict[str, torch.Tensor]:
+        """The loss values of a fused step from what ``forward_backward`` returned.  ``mono_stats``: the statistics of the
+        monocular depth term; default = those of the last ``forward_backward`` when ``tile_loss`` is that call's."""
         c = self.config
         H, W = view.rgb.shape[:2]
         t = tile_loss.sum(0)
         main = t[0]
         if ssim_sum is not None:   # per-block partial sums (or an already reduced scalar)
             main = main + c.ssim_lambda * (1 - ssim_sum.sum() / (3 * H * W))
-        return {"main_loss": main, "depth_loss": t[1]}
+        out = {"main_loss": main, "depth_loss": t[1]}
+        if mono_stats is None and self.last.get("tile_loss") is tile_loss:
+            mono_stats = self.last.get("mono_stats")
+        if mono_stats is not None:
+            out["mono_depth_loss"] = mono_stats[7]    # weight * (1 - rho), weight = mono_depth_mult
+        return out
 
     def spatial_sort(self) -> torch.Tensor:
         """Put the Gaussians (parameters, gradients, Adam moments, densification statistics) in 3-D

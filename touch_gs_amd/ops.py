@@ -917,3 +917,53 @@ def ssim_fwd_bwd(img, gt, weight: float = 1.0, want_grad: bool = True, reduce: b
     check(lib.tgs_ssim_fwd_bwd(W, H, ptr(img), ptr(gt), C.c_float(weight), ptr(bp), ptr(v_img),
                                ptr(scratch), _stream()), "tgs_ssim_fwd_bwd")
     return (bp.sum() if reduce else bp), v_img
+
+
+# ------------------------------------------------------------------------------------------------
+# image-space loss kernels: scale-invariant monocular depth (csrc/depthcorr.hip)
+# ------------------------------------------------------------------------------------------------
+def depth_corr_fwd_bwd(depth_acc, final_T, mono, alpha_min: float = 0.5, weight: float = 1.0, want_grad: bool = True):
+    """-> (stats [8] = {n, mx, my, vx, vy, c, rho, weight * (1 - rho)}, v_depth [H,W] or None, v_alpha [H,W] or None).
+    (tgs_depth_corr_fwd_bwd)
+
+    rho = Pearson correlation of the expected depth ``depth_acc / max(1 - final_T, 1e-10)`` and the raw monocular map
+    ``mono`` (any positive scale, any shift; 0 = no value) over the pixels with ``mono > 0`` and
+    ``1 - final_T >= alpha_min``.  ``v_depth`` / ``v_alpha`` = gradient of ``weight * (1 - rho)`` with respect to
+    ``depth_acc`` / ``1 - final_T``: the upstream images :func:`rasterize_bwd` takes.  A degenerate frame (fewer than two
+    valid pixels, or no variance) has rho = 0, loss 0 and zero gradients.  ``want_grad=False``: forward only.  No host sync.
+    """
+    lib = _lib.load()
+    depth_acc, final_T, mono = _f32c(depth_acc.detach()), _f32c(final_T.detach()), _f32c(mono)
+    if depth_acc.dim() != 2 or depth_acc.shape != final_T.shape or depth_acc.shape != mono.shape:
+        raise ValueError(f"depth_acc, final_T and mono must be [H,W] alike, got {tuple(depth_acc.shape)}, "
+                         f"{tuple(final_T.shape)}, {tuple(mono.shape)}")
+    H, W = depth_acc.shape
+    dev = depth_acc.device
+    tiles = torch.empty(((H + 15) // 16) * ((W + 15) // 16), 8, dtype=torch.float32, device=dev)
+    stats = torch.empty(8, dtype=torch.float32, device=dev)
+    v_depth = torch.empty(H, W, dtype=torch.float32, device=dev) if want_grad else None
+    v_alpha = torch.empty(H, W, dtype=torch.float32, device=dev) if want_grad else None
+    check(lib.tgs_depth_corr_fwd_bwd(W, H, ptr(depth_acc), ptr(final_T), ptr(mono), C.c_float(alpha_min), C.c_float(weight),
+                                     ptr(tiles), ptr(stats), ptr(v_depth), ptr(v_alpha), _stream()), "tgs_depth_corr_fwd_bwd")
+    return stats, v_depth, v_alpha
+
+
+class _DepthCorrelation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth_acc, alpha, mono, alpha_min):
+        # 1 - (1 - T) restores the bits of 1 - T for every T in [0, 1]: the kernel sees the alpha the renderer returned
+        stats, v_depth, v_alpha = depth_corr_fwd_bwd(depth_acc, 1.0 - alpha.detach(), mono, alpha_min, weight=-1.0)
+        ctx.save_for_backward(v_depth, v_alpha)   # weight -1: the images are d rho / d depth_acc, d rho / d alpha
+        return stats[6].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        v_depth, v_alpha = ctx.saved_tensors
+        return g * v_depth, g * v_alpha, None, None
+
+
+def depth_correlation(depth_acc, alpha, mono, alpha_min: float = 0.5):
+    """Pearson correlation rho (device scalar, differentiable in ``depth_acc`` and ``alpha``) between the expected depth
+    ``depth_acc / max(alpha, 1e-10)`` and ``mono`` over the pixels with ``mono > 0`` and ``alpha >= alpha_min``
+    (:func:`depth_corr_fwd_bwd`); ``depth_acc`` / ``alpha`` as :func:`render` returns them.  No host sync."""
+    return _DepthCorrelation.apply(depth_acc, alpha, mono, alpha_min)

@@ -151,6 +151,13 @@ def main(argv=None):
                     help="reference: the reference's flags mean what they mean there (uncertainty floor 0, no unseen cull). "
                          "few-view: the two additions that make touch-cloud seeds + a random fill train in the 8-13 view "
                          "regime (DESIGN.md section 10: --uncertainty-floor 0.05, --cull-unseen); explicit flags win")
+    ap.add_argument("--mono-depth-dir", type=str, default=None,
+                    help="folder under --data with one raw monocular depth map per image (<image stem>.png uint16 or .npy, "
+                         "e.g. zoe_depth): supervises through the scale-invariant correlation term, no depth sensor needed")
+    ap.add_argument("--mono-depth-mult", type=float, default=0.0,
+                    help="weight of mono_depth_mult * (1 - Pearson correlation of rendered depth and the monocular map); 0 = off")
+    ap.add_argument("--mono-depth-alpha-min", type=float, default=0.5,
+                    help="pixels with less accumulated opacity than this stay out of the correlation")
     ap.add_argument("--max-num-iterations", type=int, default=30000)
     ap.add_argument("--steps-per-save", type=int, default=2000)
     ap.add_argument("--steps-per-eval", type=int, default=500)
@@ -206,7 +213,9 @@ def main(argv=None):
     else:
         from .dataset import Scene
         scene = Scene(args.data, args.train_split_fraction, dev, uncertainty_scaling=args.uncertainty_scaling,
-                      uncertainty_floor=args.uncertainty_floor)
+                      uncertainty_floor=args.uncertainty_floor, mono_depth_dir=args.mono_depth_dir)
+        if args.mono_depth_mult > 0 and not any(v.mono_depth is not None for v in scene.views):
+            raise SystemExit("--mono-depth-mult > 0 needs --mono-depth-dir with at least one map")
         views, i_train, i_eval = scene.views, list(scene.i_train), list(scene.i_eval)
         params = init_params(args.num_gaussians, K, dev, scene.seed_points(), extent=args.random_extent, seed=args.seed,
                              seed_fraction=args.seed_fraction)
@@ -214,7 +223,8 @@ def main(argv=None):
     cfg = ModelConfig(sh_degree=args.sh_degree, depth_loss_mult=args.depth_loss_mult,
                       depth_loss_type=args.depth_loss_type, uncertainty_weight=args.uncertainty_weight,
                       spatial_sort=not args.no_spatial_sort, num_downscales=args.num_downscales,
-                      resolution_schedule=args.resolution_schedule)
+                      resolution_schedule=args.resolution_schedule, mono_depth_mult=args.mono_depth_mult,
+                      mono_depth_alpha_min=args.mono_depth_alpha_min)
     model = DepthGaussianSplattingModel(cfg, params)
     if cfg.spatial_sort:
         model.spatial_sort()
