@@ -582,6 +582,30 @@ int tgs_depth_corr_fwd_bwd(int W, int H, const float* out_depth, const float* fi
                            float alpha_min, float weight, float* tile_moments, float* stats,
                            float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/, void* stream);
 
+/* The same loss with a PATCH-WISE (local) term beside the global one (an ADDITION within TGS_VERSION 320):
+ *         L = weight_global * (1 - rho) + weight_local * (1 - rho_bar),   rho_bar = mean of rho_p over the ACTIVE patches.
+ *     Pixels, x, y, alpha and validity as above.  A patch is patch_tiles x patch_tiles (1...16) tiles of 16 x 16 pixels on a
+ *     grid whose origin is shifted by (off_x, off_y) tiles, 0 <= off < patch_tiles: tile (tx, ty) belongs to patch
+ *     ((tx + off_x) / patch_tiles, (ty + off_y) / patch_tiles), PW = ceil((TW + off_x) / patch_tiles) patches per row, PH
+ *     likewise; border patches are partial.  Per patch, over its valid pixels: n_p, means, vx_p, vy_p, c_p (centred, / n_p),
+ *     rho_p = c_p / sqrt(vx_p vy_p), beta_p = c_p / vx_p.  A patch is ACTIVE iff n_p >= min_count, vx_p >= min_var_ratio * vx and
+ *     vy_p >= min_var_ratio * vy (vx, vy: the global variances stats[3], stats[4]), vx_p vy_p > 0 and finite, and the
+ *     global frame is not degenerate.  The gates are constants of the gradient, as validity is:
+ *         g_i = g_glob,i - (weight_local / A) ((y_i - my_p) - beta_p (x_i - mx_p)) / (n_p sqrt(vx_p vy_p))   on an active patch,
+ *     A = the number of active patches; with A = 0 the local loss and its gradient are 0.
+ * out: stats[16] = {[0..7] as tgs_depth_corr_fwd_bwd with weight = weight_global, bit for bit; [8] patches with
+ *      n_p >= min_count; [9] A; [10] rho_bar; [11] weight_local * (1 - rho_bar); [12] = [7] + [11]; [13..15] 0};
+ *      patch_stats[PW * PH * 8] = per patch {active (1 / 0), mx_p, my_p, beta_p, 1 / (n_p sqrt(vx_p vy_p)), rho_p, n_p,
+ *      n_p >= min_count (1 / 0)}, beta / the scale / rho 0 on an inactive patch;  v_depth, v_alpha as above (both NULL =
+ *      forward only: four launches instead of five).
+ * tmp: tile_moments[tgs_num_tiles * 8] floats.  tile_moments, patch_stats and stats are 16-byte aligned.
+ * min_count >= 2; min_var_ratio >= 0 and finite.  No float atomics: the same inputs give the same bits. */
+int tgs_depth_corr_local_fwd_bwd(int W, int H, const float* out_depth, const float* final_T, const float* mono,
+                                 float alpha_min, float weight_global, float weight_local, int patch_tiles, int off_x,
+                                 int off_y, int min_count, float min_var_ratio, float* tile_moments, float* patch_stats,
+                                 float* stats /*[16]*/, float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/,
+                                 void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

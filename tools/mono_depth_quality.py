@@ -7,14 +7,19 @@ touch_gs_amd.prepare), in the few-view regime -- the reference's bunny_real flag
     touch_only         transforms.json registers touch_depth/ + touch_var/: the touched patches alone
     touch_plus_mono    the same + the RAW zoe_depth/ maps through --mono-depth-dir / --mono-depth-mult: no RealSense,
                        no alignment step
+    touch_plus_mono_local   the same + the patch-wise term (--mono-depth-local-mult, global 0.1 and local 0.1)
     aligned_fused      today's pipeline: ZoeDepth aligned to 1 % of the RealSense depth and fused with the touch maps
                        (fused_output_dir/ + fused_output_dir_uncertainty/)
 
 Every run is evaluated by run_eval under IS_REAL_WORLD on the held-out views (psnr, depth_mse against the run's own
 supervision maps, gt_depth_mse against the sensor) and against the analytic depth (exact_depth_mse: the one number whose
-reference is the same for the three).  Whichever way the comparison comes out, the numbers are written as measured.
+reference is the same for all runs).  Whichever way the comparison comes out, the numbers are written as measured.
 
-    python tools/mono_depth_quality.py [--root DIR] [--iters 30000] [--mono-depth-mult 0.1] [--out profiles/mono_depth_quality.json]
+    python tools/mono_depth_quality.py [--root DIR] [--iters 30000] [--mono-depth-mult 0.1] [--mono-depth-local-mult 0.1]
+                                       [--out profiles/mono_depth_quality.json]
+
+profiles/mono_depth_quality.json is the record of the three runs before the patch-wise term existed;
+profiles/mono_depth_local_quality.json holds the four.
 """
 import argparse, json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,13 +35,14 @@ ap.add_argument("--width", type=int, default=1280)
 ap.add_argument("--iters", type=int, default=30000)
 ap.add_argument("--num-gaussians", type=int, default=100000)
 ap.add_argument("--mono-depth-mult", type=float, default=0.1)
+ap.add_argument("--mono-depth-local-mult", type=float, default=0.1)
 ap.add_argument("--out", default=os.path.join("profiles", "mono_depth_quality.json"))
 args = ap.parse_args()
 if not torch.cuda.is_available():
     raise SystemExit("tools/mono_depth_quality.py trains: it needs the GPU")
 root = args.root or tempfile.mkdtemp(prefix="mdq_")
 out = dict(tool="tools/mono_depth_quality.py", device=torch.cuda.get_device_name(0), flags="bunny_real", preset="few-view",
-           iters=args.iters, mono_depth_mult=args.mono_depth_mult, views=args.views, width=args.width)
+           iters=args.iters, mono_depth_mult=args.mono_depth_mult, mono_depth_local_mult=args.mono_depth_local_mult, views=args.views, width=args.width)
 if not os.path.exists(os.path.join(root, "transforms.json")):
     t = time.perf_counter()
     out["capture"] = A.write_raw_capture(root, n_views=args.views, W=args.width, H=args.width * 9 // 16, device="cuda")
@@ -50,6 +56,7 @@ mono = ["--mono-depth-dir", "zoe_depth", "--mono-depth-mult", str(args.mono_dept
 RUNS = {   # name -> (depth dir, uncertainty dir registered in transforms.json, extra trainer flags)
     "touch_only": ("touch_depth", "touch_var", []),
     "touch_plus_mono": ("touch_depth", "touch_var", mono),
+    "touch_plus_mono_local": ("touch_depth", "touch_var", mono + ["--mono-depth-local-mult", str(args.mono_depth_local_mult)]),
     "aligned_fused": ("fused_output_dir", "fused_output_dir_uncertainty", []),
 }
 KEYS = ("psnr", "ssim", "depth_mse", "gt_depth_mse", "gt_object_depth_mse", "exact_depth_mse", "exact_object_depth_mse",

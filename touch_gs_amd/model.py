@@ -52,6 +52,16 @@ class ModelConfig:
     # near-empty pixel is not a depth, and one such outlier wrecks a correlation.  0 = off: no launch, nothing changes
     mono_depth_mult: float = 0.0
     mono_depth_alpha_min: float = 0.5
+    # patch-wise (local) term beside it  mono_depth_local_mult * (1 - mean over the active patches of rho_p)
+    # (ops.depth_corr_local_fwd_bwd): a monocular network is affine-consistent only locally.  0 = off,
+    # independent of mono_depth_mult.  Patches of mono_depth_patch_tiles x mono_depth_patch_tiles tiles (8 = 128 pixels) on a
+    # grid that moves by one tile per step (patch_offset); a patch counts with at least mono_depth_patch_min_fill of its
+    # area valid and both variances at least mono_depth_patch_min_var of the image's (1e-3: a spread under about 3 % of
+    # the image's -- a hyper-parameter, run at this one value)
+    mono_depth_local_mult: float = 0.0
+    mono_depth_patch_tiles: int = 8
+    mono_depth_patch_min_fill: float = 0.25
+    mono_depth_patch_min_var: float = 1e-3
     sh_degree_interval: int = 1000
     # Splatfacto's coarse-to-fine schedule (num_downscales 2, resolution_schedule 250): training
     # starts on images downscaled by 2^num_downscales and doubles the resolution every resolution_schedule steps.
@@ -263,13 +273,31 @@ class DepthGaussianSplattingModel:
             loss["main_loss"] = loss["main_loss"] + c.ssim_lambda * (1 - _SSIM.apply(outputs["rgb"], view.rgb))
         if c.depth_loss_mult > 0 and view.depth is not None:
             loss["depth_loss"] = c.depth_loss_mult * self.depth_loss(outputs["depth_acc"], outputs["alpha"], view)
-        if self.mono_depth_active(view):
+        if self.mono_depth_local_active(view):
+            rho, rho_bar = ops.depth_correlation_local(outputs["depth_acc"], outputs["alpha"], view.mono_depth,
+                                                       c.mono_depth_alpha_min, c.mono_depth_patch_tiles, self.patch_offset(),
+                                                       c.mono_depth_patch_min_fill, c.mono_depth_patch_min_var)
+            if c.mono_depth_mult > 0:
+                loss["mono_depth_loss"] = c.mono_depth_mult * (1 - rho)
+            loss["mono_depth_local_loss"] = c.mono_depth_local_mult * (1 - rho_bar)
+        elif self.mono_depth_active(view):
             rho = ops.depth_correlation(outputs["depth_acc"], outputs["alpha"], view.mono_depth, c.mono_depth_alpha_min)
             loss["mono_depth_loss"] = c.mono_depth_mult * (1 - rho)
         return loss
 
     def mono_depth_active(self, view: View) -> bool:
         return self.config.mono_depth_mult > 0 and view.mono_depth is not None
+
+    def mono_depth_local_active(self, view: View) -> bool:
+        return self.config.mono_depth_local_mult > 0 and view.mono_depth is not None
+
+    def patch_offset(self, step: Optional[int] = None):
+        """(off_x, off_y), in tiles, of the patch grid of the local monocular depth term at ``step`` (default: the current
+        one): off_x = step % k, off_y = (step // k) % k.  All k^2 alignments in turn; no RNG, no sync, the same on resume.
+        A step graph (``capture_step_graphs``) replays the offset its view was captured with."""
+        k = self.config.mono_depth_patch_tiles
+        step = self.step if step is None else step
+        return step % k, (step // k) % k
 
     @torch.no_grad()
     def get_metrics_dict(self, outputs, view: View) -> Dict[str, torch.Tensor]:
@@ -348,7 +376,14 @@ class DepthGaussianSplattingModel:
         rgb, depth_acc, fT, fidx = ops.rasterize_fwd(cam, splats, sorted_gid, tile_start, opts=self.tuning.raster_opts())
         v_img, ssim_sum = None, None
         mono_stats = v_depth = v_alpha = None
-        if self.mono_depth_active(view):   # image-space term beside K7, which adds its fused terms on top of the two images
+        patch_off = None
+        if self.mono_depth_local_active(view):   # global + patch-wise term in one op: the same two images
+            patch_off = self.patch_offset()
+            mono_stats, v_depth, v_alpha = ops.depth_corr_local_fwd_bwd(
+                depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min, weight_global=max(c.mono_depth_mult, 0.0),
+                weight_local=c.mono_depth_local_mult, patch_tiles=c.mono_depth_patch_tiles, offset=patch_off,
+                min_fill=c.mono_depth_patch_min_fill, min_var_ratio=c.mono_depth_patch_min_var)
+        elif self.mono_depth_active(view):   # image-space term beside K7, which adds its fused terms on top of the two images
             mono_stats, v_depth, v_alpha = ops.depth_corr_fwd_bwd(depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min,
                                                                   weight=c.mono_depth_mult)
         if (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles and mono_stats is None
@@ -390,6 +425,8 @@ class DepthGaussianSplattingModel:
                          tile_loss=tile_loss, ssim_sum=ssim_sum, status=status, guard=guard, view=view)
         if mono_stats is not None:
             self.last["mono_stats"] = mono_stats
+        if patch_off is not None:
+            self.last["mono_patch_offset"] = patch_off
         return tile_loss, ssim_sum
 
     def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None) -> Dict[str, torch.Tensor]:
@@ -405,7 +442,10 @@ class DepthGaussianSplattingModel:
         if mono_stats is None and self.last.get("tile_loss") is tile_loss:
             mono_stats = self.last.get("mono_stats")
         if mono_stats is not None:
-            out["mono_depth_loss"] = mono_stats[7]    # weight * (1 - rho), weight = mono_depth_mult
+            if mono_stats.numel() == 8 or c.mono_depth_mult > 0:
+                out["mono_depth_loss"] = mono_stats[7]    # weight * (1 - rho), weight = mono_depth_mult
+            if mono_stats.numel() == 16:                  # the local term was active in that step
+                out["mono_depth_local_loss"] = mono_stats[11]     # mono_depth_local_mult * (1 - rho_bar)
         return out
 
     def spatial_sort(self) -> torch.Tensor:

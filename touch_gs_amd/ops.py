@@ -13,6 +13,7 @@ Every op runs the HIP kernels; there is no eager/CPU fallback (tensors must be o
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -967,3 +968,76 @@ def depth_correlation(depth_acc, alpha, mono, alpha_min: float = 0.5):
     ``depth_acc / max(alpha, 1e-10)`` and ``mono`` over the pixels with ``mono > 0`` and ``alpha >= alpha_min``
     (:func:`depth_corr_fwd_bwd`); ``depth_acc`` / ``alpha`` as :func:`render` returns them.  No host sync."""
     return _DepthCorrelation.apply(depth_acc, alpha, mono, alpha_min)
+
+
+# ------------------------------------------------------------------------------------------------
+# the same with a patch-wise (local) correlation term beside the global one (DESIGN 5.1h)
+# ------------------------------------------------------------------------------------------------
+def depth_corr_patch_min_count(patch_tiles: int, min_fill: float) -> int:
+    """The count gate of a patch of ``patch_tiles`` x ``patch_tiles`` tiles: max(2, ceil(min_fill (16 patch_tiles)^2))."""
+    return max(2, math.ceil(min_fill * (16 * patch_tiles) ** 2))
+
+
+def depth_corr_local_fwd_bwd(depth_acc, final_T, mono, alpha_min: float = 0.5, weight_global: float = 1.0,
+                             weight_local: float = 1.0, patch_tiles: int = 8, offset=(0, 0), min_fill: float = 0.25,
+                             min_var_ratio: float = 1e-3, want_grad: bool = True, return_patches: bool = False):
+    """-> (stats [16], v_depth [H,W] or None, v_alpha [H,W] or None[, patch_stats [PH, PW, 8]]).
+    (tgs_depth_corr_local_fwd_bwd)
+
+    ``weight_global * (1 - rho) + weight_local * (1 - rho_bar)``: rho as in :func:`depth_corr_fwd_bwd`, rho_bar the mean
+    of the per-patch correlations over the ACTIVE patches of ``patch_tiles`` x ``patch_tiles`` tiles (16 ``patch_tiles``
+    pixels on a side), the grid shifted by ``offset = (off_x, off_y)`` tiles.  A patch is active with at least
+    ``min_fill`` of its full area valid and both its variances at least ``min_var_ratio`` of the image's.
+    stats = {[0..7] as the global op with ``weight = weight_global``, [8] patches that pass the count gate, [9] active
+    patches A, [10] rho_bar, [11] weight_local (1 - rho_bar), [12] total loss, [13..15] 0}; patch_stats per patch =
+    {active, mx, my, beta, 1 / (n sqrt(vx vy)), rho, n, passes the count gate}.  No host sync.
+    """
+    lib = _lib.load()
+    depth_acc, final_T, mono = _f32c(depth_acc.detach()), _f32c(final_T.detach()), _f32c(mono)
+    if depth_acc.dim() != 2 or depth_acc.shape != final_T.shape or depth_acc.shape != mono.shape:
+        raise ValueError(f"depth_acc, final_T and mono must be [H,W] alike, got {tuple(depth_acc.shape)}, "
+                         f"{tuple(final_T.shape)}, {tuple(mono.shape)}")
+    k, (off_x, off_y) = int(patch_tiles), (int(o) for o in offset)
+    if not 1 <= k <= 16 or not (0 <= off_x < k and 0 <= off_y < k):
+        raise ValueError(f"patch_tiles must be 1...16 and the offset in [0, patch_tiles), got {patch_tiles}, {tuple(offset)}")
+    H, W = depth_acc.shape
+    dev = depth_acc.device
+    TW, TH = (W + 15) // 16, (H + 15) // 16
+    PW, PH = (TW + off_x + k - 1) // k, (TH + off_y + k - 1) // k
+    tiles = torch.empty(TW * TH, 8, dtype=torch.float32, device=dev)
+    patches = torch.empty(PH, PW, 8, dtype=torch.float32, device=dev)
+    stats = torch.empty(16, dtype=torch.float32, device=dev)
+    v_depth = torch.empty(H, W, dtype=torch.float32, device=dev) if want_grad else None
+    v_alpha = torch.empty(H, W, dtype=torch.float32, device=dev) if want_grad else None
+    check(lib.tgs_depth_corr_local_fwd_bwd(W, H, ptr(depth_acc), ptr(final_T), ptr(mono), C.c_float(alpha_min),
+                                           C.c_float(weight_global), C.c_float(weight_local), k, off_x, off_y,
+                                           depth_corr_patch_min_count(k, min_fill), C.c_float(min_var_ratio), ptr(tiles),
+                                           ptr(patches), ptr(stats), ptr(v_depth), ptr(v_alpha), _stream()),
+          "tgs_depth_corr_local_fwd_bwd")
+    return (stats, v_depth, v_alpha, patches) if return_patches else (stats, v_depth, v_alpha)
+
+
+class _DepthCorrelationLocal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth_acc, alpha, mono, alpha_min, patch_tiles, offset, min_fill, min_var_ratio):
+        # two calls with unit weights (a slow path): the images of the first are d rho / d (depth_acc, alpha), those of the
+        # second d rho_bar / d (depth_acc, alpha)
+        fT = 1.0 - alpha.detach()
+        kw = dict(patch_tiles=patch_tiles, offset=offset, min_fill=min_fill, min_var_ratio=min_var_ratio)
+        stats, gd, ga = depth_corr_local_fwd_bwd(depth_acc, fT, mono, alpha_min, -1.0, 0.0, **kw)
+        _, ld, la = depth_corr_local_fwd_bwd(depth_acc, fT, mono, alpha_min, 0.0, -1.0, **kw)
+        ctx.save_for_backward(gd, ga, ld, la)
+        return stats[6].clone(), stats[10].clone()
+
+    @staticmethod
+    def backward(ctx, g_rho, g_bar):
+        gd, ga, ld, la = ctx.saved_tensors
+        return g_rho * gd + g_bar * ld, g_rho * ga + g_bar * la, None, None, None, None, None, None
+
+
+def depth_correlation_local(depth_acc, alpha, mono, alpha_min: float = 0.5, patch_tiles: int = 8, offset=(0, 0),
+                            min_fill: float = 0.25, min_var_ratio: float = 1e-3):
+    """(rho, rho_bar): the global Pearson correlation of :func:`depth_correlation` and the mean correlation over the
+    active patches (:func:`depth_corr_local_fwd_bwd`), device scalars differentiable in ``depth_acc`` and ``alpha`` with the
+    gates held constant.  No host sync."""
+    return _DepthCorrelationLocal.apply(depth_acc, alpha, mono, alpha_min, patch_tiles, tuple(offset), min_fill, min_var_ratio)

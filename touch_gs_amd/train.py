@@ -158,6 +158,14 @@ def main(argv=None):
                     help="weight of mono_depth_mult * (1 - Pearson correlation of rendered depth and the monocular map); 0 = off")
     ap.add_argument("--mono-depth-alpha-min", type=float, default=0.5,
                     help="pixels with less accumulated opacity than this stay out of the correlation")
+    ap.add_argument("--mono-depth-local-mult", type=float, default=0.0,
+                    help="weight of the patch-wise term: (1 - mean Pearson correlation over patches of the image); 0 = off, "
+                         "independent of --mono-depth-mult")
+    ap.add_argument("--mono-depth-patch-tiles", type=int, default=8, help="patch side in 16-pixel tiles (1...16; 8 = 128 pixels)")
+    ap.add_argument("--mono-depth-patch-min-fill", type=float, default=0.25,
+                    help="a patch counts with at least this share of its area valid")
+    ap.add_argument("--mono-depth-patch-min-var", type=float, default=1e-3,
+                    help="a patch counts with both variances at least this share of the image's")
     ap.add_argument("--max-num-iterations", type=int, default=30000)
     ap.add_argument("--steps-per-save", type=int, default=2000)
     ap.add_argument("--steps-per-eval", type=int, default=500)
@@ -214,7 +222,7 @@ def main(argv=None):
         from .dataset import Scene
         scene = Scene(args.data, args.train_split_fraction, dev, uncertainty_scaling=args.uncertainty_scaling,
                       uncertainty_floor=args.uncertainty_floor, mono_depth_dir=args.mono_depth_dir)
-        if args.mono_depth_mult > 0 and not any(v.mono_depth is not None for v in scene.views):
+        if (args.mono_depth_mult > 0 or args.mono_depth_local_mult > 0) and not any(v.mono_depth is not None for v in scene.views):
             raise SystemExit("--mono-depth-mult > 0 needs --mono-depth-dir with at least one map")
         views, i_train, i_eval = scene.views, list(scene.i_train), list(scene.i_eval)
         params = init_params(args.num_gaussians, K, dev, scene.seed_points(), extent=args.random_extent, seed=args.seed,
@@ -224,7 +232,9 @@ def main(argv=None):
                       depth_loss_type=args.depth_loss_type, uncertainty_weight=args.uncertainty_weight,
                       spatial_sort=not args.no_spatial_sort, num_downscales=args.num_downscales,
                       resolution_schedule=args.resolution_schedule, mono_depth_mult=args.mono_depth_mult,
-                      mono_depth_alpha_min=args.mono_depth_alpha_min)
+                      mono_depth_alpha_min=args.mono_depth_alpha_min, mono_depth_local_mult=args.mono_depth_local_mult,
+                      mono_depth_patch_tiles=args.mono_depth_patch_tiles, mono_depth_patch_min_fill=args.mono_depth_patch_min_fill,
+                      mono_depth_patch_min_var=args.mono_depth_patch_min_var)
     model = DepthGaussianSplattingModel(cfg, params)
     if cfg.spatial_sort:
         model.spatial_sort()
