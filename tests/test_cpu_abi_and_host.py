@@ -602,6 +602,61 @@ def test_c_abi_refuses_a_short_tile_start_buffer():
         assert rc == -1 and b"tgs_tile_start_len" in lib.tgs_last_error(), lib.tgs_last_error()
 
 
+def test_next_front_entry_points_refuse_bad_arguments():
+    """The three entry points that also run the NEXT view's K1 (fused K8 + Adam with front prefetch, the geometry Adam of
+    the data-parallel step, its fused tail) refuse a null / zeroed next camera, a 4081-px side, a null front buffer and a
+    capacity of 2^31 with TGS_E_ARG and a message that names the fault -- before any launch, so this runs without a GPU."""
+    from touch_gs_amd import _lib
+    lib = _lib.load()
+    fake = C.c_void_p(0x1000)      # never dereferenced: every check here precedes the first launch
+    spec = C.byref(_lib.TgsAdamSpec())
+    N = 256
+
+    def camera(W=64, H=48):
+        cam = _lib.TgsCamera()
+        cam.W, cam.H, cam.fx, cam.fy, cam.cx, cam.cy = W, H, 50.0, 50.0, W / 2, H / 2
+        for i in (0, 5, 10, 15):
+            cam.viewmat[i] = 1.0
+        return C.byref(cam)
+
+    def k8_front(nxt, splats_next, capacity, N=N):
+        return lib.tgs_project_bwd_adam_next_front(camera(), N, 16, 3, fake, fake, fake, spec, fake, fake, fake, None, None,
+                                                   nxt, fake, fake, 1, splats_next, None, fake, fake, capacity, fake, fake,
+                                                   None, 0, None)
+
+    def geom(nxt, splats_next, capacity, N=N):
+        return lib.tgs_adam_geom_project_next(nxt, N, 16, 3, fake, fake, fake, fake, spec, 1.0, None, fake, 1, splats_next,
+                                              None, fake, fake, capacity, fake, fake, None, 0, None)
+
+    def tail(nxt, splats_next, capacity, N=N):
+        return lib.tgs_adam_sh_gathered_geom_project_next(nxt, 2, N, 16, 3, fake, fake, 1, None, None, fake, fake, spec, 1.0,
+                                                          None, fake, 1, splats_next, None, fake, fake, capacity, fake,
+                                                          fake, None, 0, None)
+
+    for call, name, capacity_word in ((k8_front, b"tgs_project_bwd_adam_next_front", b"capacity"),
+                                      (geom, b"tgs_adam_geom_project_next", b"size"),
+                                      (tail, b"tgs_adam_sh_gathered_geom_project_next", b"size")):
+        def refused(rc, word):     # the message names the entry point the caller used and the fault
+            msg = lib.tgs_last_error()
+            assert rc == -1 and msg.startswith(name + b":") and word in msg, (rc, msg)
+
+        for nxt in (None, C.byref(_lib.TgsCamera())):
+            refused(call(nxt, fake, 1024), b"next camera")
+        for W, H in ((4081, 48), (64, 4081)):
+            refused(call(camera(W, H), fake, 1024), b"4080")
+        refused(call(camera(), None, 1024), b"front buffer")
+        refused(call(camera(), fake, 1 << 31), capacity_word)
+        # an empty model: still refused for its camera and its capacity; the null front buffer is refused by the K8 entry
+        # point, which checks it before its N == 0 return, and passes the two data-parallel ones, which check it after
+        refused(call(None, fake, 1024, N=0), b"next camera")
+        refused(call(camera(), fake, 1 << 31, N=0), capacity_word)
+        if call is k8_front:
+            refused(call(camera(), None, 1024, N=0), b"front buffer")
+        else:
+            assert call(camera(), None, 1024, N=0) == 0
+        assert call(camera(), fake, 1024, N=0) == 0
+
+
 def test_raster_defaults_are_process_wide_and_opts_override_them():
     """The tgs_set_* calls only move the process-wide DEFAULTS (atomic words); they round-trip, and a TgsRasterOpts with
     every field -1 is what NULL means."""

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds a variant of libtgs_hip.so for same-box A/B runs (tools/ab.py / tools/abn.py):
 #   bash tools/build_variant.sh <name> [extra hipcc flags, e.g. -DTGS_GID_PREFETCH] [RASTER=<path to an alternative raster.hip>]
-# Output: build_ab/<name>.so.  Objects of unchanged translation units are taken from touch_gs_amd/lib/.
+# Output: build_ab/<name>.so, from every csrc/*.hip (the per-file flags below mirror csrc/build.sh).
 set -e
 NAME=$1; shift
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
@@ -20,8 +20,9 @@ for a in "$@"; do
   esac
 done
 pids=()
-for s in api project binning raster optim imgloss peer; do
-  f=${ALT[$s]:-$SRC/$s.hip}
+for src in $SRC/*.hip; do     # every translation unit of the library: _lib.py binds all its symbols at load time
+  s=$(basename $src .hip)
+  f=${ALT[$s]:-$src}
   /opt/rocm/bin/hipcc $FLAGS ${EXTRA[$s]} "${ARGS[@]}" -c "$f" -o $OUT/$s.o &
   pids+=($!)
 done

@@ -49,3 +49,14 @@ print("Adam geom  us", timeit(lambda: opt.step_range(0, ge, 1.0)))
 for world in (1, 2, 4, 8):
     allc = block.repeat(world).contiguous()
     print(f"Adam SH gathered world={world} us", timeit(lambda: opt.step_sh_gathered(world, deg, allc, 1.0 / world)))
+# the tail of the step: geometry Adam + the next view's K1, alone and in one launch with the SH Adam (fused tail)
+nxt = make_view(N, W, H, deg, 1236, dev, view=1, n_views=8).cam
+budget = ops.IntersectBudget(capacity=model.budget.capacity, sync=False)
+pf = ops.ColorPrefetch(N, dev).arm(nxt, deg, front=ops.FrontBuffers(nxt, N, budget.capacity, False, dev), budget=budget,
+                                   colors_valid=False)
+print("Adam geom + next K1 us", timeit(lambda: opt.step_geom_and_project_next(deg, 1.0, None, pf)))
+for world in (1, 2, 4, 8):
+    allc = block.repeat(world).contiguous()
+    print(f"fused tail world={world} us", timeit(lambda: opt.step_sh_gathered_geom_and_project_next(
+        world, deg, [(0, N)], [allc], 1.0 / world, None, pf)))
+assert int(budget.sticky_word(dev).item()) == 0, "the next frame's K1 overflowed its intersection budget"

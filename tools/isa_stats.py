@@ -22,7 +22,9 @@ for name, ins in body.items():
     short = re.sub(r"^_ZN?\d*(_GLOBAL__N_1)?\d*", "", name)[:48]
     print(f"{short:48s} total {len(ins):5d} valu {f('v_'):5d} salu {f('s_'):5d} ds {f('ds_'):4d} | exp {f('v_exp')} rcp {f('v_rcp')} "
           f"cndmask {f('v_cndmask')} cmp {f('v_cmp')} fma {f('v_fma') + f('v_fmac')} branch {f('s_cbranch')}")
-for m in re.finditer(r"\.name:\s+(\S+)(.*?)\.wavefront_size", asm, re.S):
-    v = re.search(r"\.vgpr_count:\s+(\d+)", m.group(2)); a = re.search(r"\.agpr_count:\s+(\d+)", m.group(2))
-    l = re.search(r"\.group_segment_fixed_size:\s+(\d+)", m.group(2)); sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", m.group(2))
-    print(f"  {m.group(1)[:70]:70s} vgpr {v.group(1) if v else '?'} agpr {a.group(1) if a else '?'} lds {l.group(1) if l else '?'} spill {sp.group(1) if sp else '?'}")
+for m in re.finditer(r"\.agpr_count:.*?\.wavefront_size", asm, re.S):   # one kernel's metadata: its keys are sorted by name
+    k = m.group(0)
+    name = re.search(r"\.name:\s+(\S+)", k).group(1)
+    v = re.search(r"\.vgpr_count:\s+(\d+)", k); a = re.search(r"\.agpr_count:\s+(\d+)", k)
+    l = re.search(r"\.group_segment_fixed_size:\s+(\d+)", k); sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", k)
+    print(f"  {name[:70]:70s} vgpr {v.group(1) if v else '?'} agpr {a.group(1) if a else '?'} lds {l.group(1) if l else '?'} spill {sp.group(1) if sp else '?'}")

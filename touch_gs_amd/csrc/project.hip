@@ -405,8 +405,8 @@ __global__ __launch_bounds__(256) void k_project_fwd_colors(
 // Data-parallel step: Adam on the 11 geometry parameters of every Gaussian from the all-reduced gradients AND the
 // next view's K1 on the result (front prefetch of the data-parallel form: there the optimizer is not fused with K8,
 // and the SH rows were stepped just before by the gathered-SH kernel, so the colour comes from the SH rows as in the
-// stand-alone K1).  Replaces k_adam on the geometry segments + the next step's k_project_fwd; same adam1, same
-// project_fwd_core on the same values: bit-identical to the two-kernel sequence.
+// stand-alone K1).  Replaces k_adam on the geometry segments + the next step's k_project_fwd; same adam1 (adam_geom,
+// tgs_adam.h), same project_fwd_core on the same values: bit-identical to the two-kernel sequence.
 template <int DEG>
 __global__ __launch_bounds__(256) void k_adam_geom_project_next(
     CamK cam, int N, int sh_stride, float* __restrict__ means, float* __restrict__ log_scales,
@@ -422,37 +422,12 @@ __global__ __launch_bounds__(256) void k_adam_geom_project_next(
   float m[3] = {0.f, 0.f, 0.f}, ls[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f};
   float ol = 0.f;
   if (g < N) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const long long e = 3ll * g + j;
-      float P = means[3 * g + j], M = exp_avg[e], V = exp_avg_sq[e];
-      adam1(ad, ad.lr_means, P, grads[e], M, V);
-      means[3 * g + j] = P; exp_avg[e] = M; exp_avg_sq[e] = V;
-      m[j] = P;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const long long e = ad.e_means + 3ll * g + j;
-      float P = log_scales[3 * g + j], M = exp_avg[e], V = exp_avg_sq[e];
-      adam1(ad, ad.lr_scales, P, grads[e], M, V);
-      log_scales[3 * g + j] = P; exp_avg[e] = M; exp_avg_sq[e] = V;
-      ls[j] = P;
-    }
-    {
-      const long long e = ad.e_scales + 4ll * g;
-      float4 Q = ld4(quats + 4 * (size_t)g), G = ld4_nt(grads + e), M = ld4_nt(exp_avg + e), V = ld4_nt(exp_avg_sq + e);
-      adam1(ad, ad.lr_quats, Q.x, G.x, M.x, V.x); adam1(ad, ad.lr_quats, Q.y, G.y, M.y, V.y);
-      adam1(ad, ad.lr_quats, Q.z, G.z, M.z, V.z); adam1(ad, ad.lr_quats, Q.w, G.w, M.w, V.w);
-      st4(quats + 4 * (size_t)g, Q); st4_nt(exp_avg + e, M); st4_nt(exp_avg_sq + e, V);
-      q[0] = Q.x; q[1] = Q.y; q[2] = Q.z; q[3] = Q.w;
-    }
-    {
-      const long long e = ad.e_quats + g;
-      float P = opac_logit[g], M = exp_avg[e], V = exp_avg_sq[e];
-      adam1(ad, ad.lr_opac, P, grads[e], M, V);
-      opac_logit[g] = P; exp_avg[e] = M; exp_avg_sq[e] = V;
-      ol = P;
-    }
+    m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];
+    ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
+    const float4 q4 = ld4(quats + 4 * (size_t)g);
+    q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+    ol = opac_logit[g];
+    adam_geom_flat(ad, g, m, ls, q, ol, grads, means, log_scales, quats, opac_logit, exp_avg, exp_avg_sq);
     sh_color<DEG>(m, cam.campos, sh + (size_t)g * sh_stride * 3, rgb);
   }
   project_fwd_core<true>(cam, N, g, m, ls, q, ol, rgb, splats, radii, group_base, tile_count, rank, status,
@@ -976,81 +951,26 @@ __global__ __launch_bounds__(256) void k_project_bwd_lds(
       st4(v_quats + 4 * (size_t)g, make_float4(vq[0], vq[1], vq[2], vq[3]));
       v_opac_logit[g] = vol;
     } else {
-      // Adam on the 11 non-SH parameters of this Gaussian (flat-buffer offsets from the layout)
-      float* ea = exp_avg; float* es = exp_avg_sq;
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const long long e = 3ll * g + j;
-        float pm = m[j], M = ea[e], V = es[e];
-        adam1(ad, ad.lr_means, pm, vm[j], M, V);
-        means[3 * g + j] = pm; ea[e] = M; es[e] = V;
-        m[j] = pm;   // the colour prefetch below looks from the NEXT camera at the UPDATED mean
-      }
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const long long e = ad.e_means + 3ll * g + j;
-        float pl = ls[j], M = ea[e], V = es[e];
-        adam1(ad, ad.lr_scales, pl, vls[j], M, V);
-        log_scales[3 * g + j] = pl; ea[e] = M; es[e] = V;
-        ls[j] = pl;
-      }
-      {
-        const long long e = ad.e_scales + 4ll * g;
-        float4 M = ld4_nt(ea + e), V = ld4_nt(es + e);
-        float4 Q = make_float4(q[0], q[1], q[2], q[3]);
-        adam1(ad, ad.lr_quats, Q.x, vq[0], M.x, V.x); adam1(ad, ad.lr_quats, Q.y, vq[1], M.y, V.y);
-        adam1(ad, ad.lr_quats, Q.z, vq[2], M.z, V.z); adam1(ad, ad.lr_quats, Q.w, vq[3], M.w, V.w);
-        st4_nt(quats + 4 * (size_t)g, Q); st4_nt(ea + e, M); st4_nt(es + e, V);
-        q[0] = Q.x; q[1] = Q.y; q[2] = Q.z; q[3] = Q.w;
-      }
-      {
-        const long long e = ad.e_quats + g;
-        float po = ol, M = ea[e], V = es[e];
-        adam1(ad, ad.lr_opac, po, vol, M, V);
-        opac_logit[g] = po; ea[e] = M; es[e] = V;
-        ol = po;
-      }
+      // Adam on the 11 non-SH parameters of this Gaussian; the colour prefetch below looks from the NEXT camera at the
+      // UPDATED mean, and the front prefetch projects the updated parameters
+      adam_geom<true>(ad, g, m, ls, q, ol, vm, vls, vq, vol, means, log_scales, quats, opac_logit, exp_avg, exp_avg_sq);
     }
   }
   if constexpr (COLOR_ONLY) return;
   __syncthreads();
-  // coalesced stream of the block's SH gradient image (2 float4 columns per thread per round so
-  // that 6 independent loads are in flight)
-  const int nf = nrows * F4;
-  for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
-    if constexpr (!FUSE_ADAM) {
+  // coalesced stream of the block's SH gradient image: out as v_sh, or through the Adam update (with a colour
+  // prefetch the updated coefficients replace the consumed gradient in the image)
+  if constexpr (!FUSE_ADAM) {
+    const int nf = nrows * F4;
+    for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
 #pragma unroll
       for (int u = 0; u < 2; u++) {
         const int f = f0 + 256 * u;
         if (f < nf) { const int row = f / F4, c4 = f - row * F4; st4(v_sh + blk + 4 * (size_t)f, ld4(lds + row * RS + 4 * c4)); }
       }
-    } else {
-      float4 P[2], M[2], V[2];
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int f = f0 + 256 * u;
-        if (f < nf) {
-          const size_t e = blk + 4 * (size_t)f;
-          P[u] = ld4_nt(sh + e); M[u] = ld4_nt(exp_avg + ad.e_opac + e); V[u] = ld4_nt(exp_avg_sq + ad.e_opac + e);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int f = f0 + 256 * u;
-        if (f < nf) {
-          const int row = f / F4, c4 = f - row * F4;
-          const float4 G = ld4(lds + row * RS + 4 * c4);
-          const size_t e = blk + 4 * (size_t)f;
-          const int c = 4 * c4;  // column of the first element inside the 3K-float row; DC = columns 0..2
-          adam1(ad, c < 3 ? ad.lr_dc : ad.lr_rest, P[u].x, G.x, M[u].x, V[u].x);
-          adam1(ad, c + 1 < 3 ? ad.lr_dc : ad.lr_rest, P[u].y, G.y, M[u].y, V[u].y);
-          adam1(ad, c + 2 < 3 ? ad.lr_dc : ad.lr_rest, P[u].z, G.z, M[u].z, V[u].z);
-          adam1(ad, ad.lr_rest, P[u].w, G.w, M[u].w, V[u].w);
-          st4_nt(sh + e, P[u]); st4_nt(exp_avg + ad.e_opac + e, M[u]); st4_nt(exp_avg_sq + ad.e_opac + e, V[u]);
-          if (nx.colors) st4(lds + row * RS + 4 * c4, P[u]);   // updated coefficients replace the consumed gradient
-        }
-      }
     }
+  } else {
+    adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, blk, nrows, F4, RS, tid, nx.colors != nullptr);
   }
   if constexpr (FUSE_ADAM) {
     // Colour prefetch: the next step's K1 needs, of the 3K updated coefficients, only the colour they
@@ -1089,6 +1009,43 @@ __global__ __launch_bounds__(256) void k_project_bwd_lds(
 // the fused K8+Adam tail.  `means` must still hold the values the forward pass used.  Each rank's
 // block carries its camera position behind the N colour gradients (written by K8), so no host data
 // is needed.
+//
+// sh_grad_gathered: the SH gradient row of one Gaussian (mean m0, m1, m2; row `local_row` of the gathered blocks, which
+// hold nb rows each) into `row`, its F4 float4s in the LDS image; the inactive bases get zeros.
+template <int DEG>
+__device__ __forceinline__ void sh_grad_gathered(int world, const float* __restrict__ v_color_all, size_t nb, int local_row,
+                                                 float m0, float m1, float m2, float* row, int F4) {
+  constexpr int K = (DEG + 1) * (DEG + 1);
+  float acc[3 * K];
+#pragma unroll
+  for (int i = 0; i < 3 * K; i++) acc[i] = 0.f;
+  const size_t blk_r = 3 * nb + 4;   // one rank's block: v_color[rows,3] | campos[3] | pad
+  for (int r = 0; r < world; r++) {
+    const float* vc = v_color_all + r * blk_r + 3 * (size_t)local_row;
+    const float* cp = v_color_all + r * blk_r + 3 * nb;
+    const float v0 = vc[0], v1 = vc[1], v2 = vc[2];
+    const float dx = m0 - cp[0], dy = m1 - cp[1], dz = m2 - cp[2];
+    const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
+    float Y[16];
+    sh_basis<DEG>(dx * inv, dy * inv, dz * inv, Y);
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      acc[3 * k] = fmaf(Y[k], v0, acc[3 * k]);
+      acc[3 * k + 1] = fmaf(Y[k], v1, acc[3 * k + 1]);
+      acc[3 * k + 2] = fmaf(Y[k], v2, acc[3 * k + 2]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 3 * K / 4; i++) st4(row + 4 * i, make_float4(acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]));
+  if constexpr ((3 * K) % 4 != 0) {   // K = 1 or 9: finish the last partial float4 with zeros
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < (3 * K) % 4; i++) t[i] = acc[(3 * K / 4) * 4 + i];
+    st4(row + (3 * K / 4) * 4, make_float4(t[0], t[1], t[2], t[3]));
+  }
+  for (int i = (3 * K + 3) / 4; i < F4; i++) st4(row + 4 * i, make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
 template <int DEG>
 __global__ __launch_bounds__(256) void k_adam_sh_gathered(
     int world, int row0, int N, int sh_stride, const float* __restrict__ means,
@@ -1097,7 +1054,6 @@ __global__ __launch_bounds__(256) void k_adam_sh_gathered(
   // rows [row0, N) of the model; the gathered blocks hold exactly these rows (N - row0 colour gradients each)
   if (ad_in.guard && ad_in.guard[1]) return;   // a rank's frame overflowed (tgs_dp_agree_overflow): no update
   const AdamK ad = adam_resolve(ad_in);
-  constexpr int K = (DEG + 1) * (DEG + 1);
   const int ROW = 3 * sh_stride, RS = ROW + 4, F4 = ROW / 4;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -1106,79 +1062,24 @@ __global__ __launch_bounds__(256) void k_adam_sh_gathered(
   const int g = g0 + tid;
   const int nrows = min(256, N - g0);
   const size_t blk = (size_t)g0 * ROW;
-  if (g < N) {
-    const float m0 = means[3 * g], m1 = means[3 * g + 1], m2 = means[3 * g + 2];
-    float acc[3 * K];
-#pragma unroll
-    for (int i = 0; i < 3 * K; i++) acc[i] = 0.f;
-    const size_t nb = (size_t)(N - row0);
-    const size_t blk_r = 3 * nb + 4;   // one rank's block: v_color[rows,3] | campos[3] | pad
-    for (int r = 0; r < world; r++) {
-      const float* vc = v_color_all + r * blk_r + 3 * (size_t)(g - row0);
-      const float* cp = v_color_all + r * blk_r + 3 * nb;
-      const float v0 = vc[0], v1 = vc[1], v2 = vc[2];
-      const float dx = m0 - cp[0], dy = m1 - cp[1], dz = m2 - cp[2];
-      const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-      float Y[16];
-      sh_basis<DEG>(dx * inv, dy * inv, dz * inv, Y);
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-        acc[3 * k] = fmaf(Y[k], v0, acc[3 * k]);
-        acc[3 * k + 1] = fmaf(Y[k], v1, acc[3 * k + 1]);
-        acc[3 * k + 2] = fmaf(Y[k], v2, acc[3 * k + 2]);
-      }
-    }
-    float* row = lds + tid * RS;
-#pragma unroll
-    for (int i = 0; i < 3 * K / 4; i++) st4(row + 4 * i, make_float4(acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]));
-    if constexpr ((3 * K) % 4 != 0) {   // K = 1 or 9: finish the last partial float4 with zeros
-      float t[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < (3 * K) % 4; i++) t[i] = acc[(3 * K / 4) * 4 + i];
-      st4(row + (3 * K / 4) * 4, make_float4(t[0], t[1], t[2], t[3]));
-    }
-    for (int i = (3 * K + 3) / 4; i < F4; i++) st4(row + 4 * i, make_float4(0.f, 0.f, 0.f, 0.f));
-  }
+  if (g < N)
+    sh_grad_gathered<DEG>(world, v_color_all, (size_t)(N - row0), g - row0, means[3 * g], means[3 * g + 1],
+                          means[3 * g + 2], lds + tid * RS, F4);
   __syncthreads();
-  const int nf = nrows * F4;
-  for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
-    float4 P[2], M[2], V[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int f = f0 + 256 * u;
-      if (f < nf) {
-        const size_t e = blk + 4 * (size_t)f;
-        P[u] = ld4_nt(sh + e); M[u] = ld4_nt(exp_avg + ad.e_opac + e); V[u] = ld4_nt(exp_avg_sq + ad.e_opac + e);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int f = f0 + 256 * u;
-      if (f < nf) {
-        const int row = f / F4, c4 = f - row * F4;
-        const float4 G = ld4(lds + row * RS + 4 * c4);
-        const size_t e = blk + 4 * (size_t)f;
-        const int c = 4 * c4;  // column inside the 3K-float row; DC = columns 0..2
-        adam1(ad, c < 3 ? ad.lr_dc : ad.lr_rest, P[u].x, G.x, M[u].x, V[u].x);
-        adam1(ad, c + 1 < 3 ? ad.lr_dc : ad.lr_rest, P[u].y, G.y, M[u].y, V[u].y);
-        adam1(ad, c + 2 < 3 ? ad.lr_dc : ad.lr_rest, P[u].z, G.z, M[u].z, V[u].z);
-        adam1(ad, ad.lr_rest, P[u].w, G.w, M[u].w, V[u].w);
-        st4_nt(sh + e, P[u]); st4_nt(exp_avg + ad.e_opac + e, M[u]); st4_nt(exp_avg_sq + ad.e_opac + e, V[u]);
-      }
-    }
-  }
+  adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, blk, nrows, F4, RS, tid, false);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Data-parallel step, fused tail (round 6): SH Adam from the gathered colour blocks + geometry Adam from the
 // all-reduced gradients + the next view's colours and K1 in ONE launch over the whole model
 // ---------------------------------------------------------------------------------------------
-// = k_adam_sh_gathered (per row chunk) followed by k_adam_geom_project_next, for a workgroup's 256 rows: the updated
-// SH rows stay in the LDS image the Adam stream has just produced, so the next camera's colour is evaluated there
-// instead of from rows re-read from HBM, the gradients of the 11 geometry parameters are read once, and four to five
-// launches become one.  Same adam1 / sh_color / project_fwd_core on the same values: bit-identical to the unfused
-// sequence.  It can only start when the geometry all-reduce has landed -- which on a node is exactly what the chunked
-// SH Adam hides under -- so the host selects it by world size (parallel.GradSync.fused_tail).
+// The bodies of k_adam_sh_gathered (per row chunk: sh_grad_gathered, adam_sh_stream) and of k_adam_geom_project_next
+// (adam_geom_flat) for a workgroup's 256 rows: the updated SH rows stay in the LDS image the Adam stream has just
+// produced, so the next camera's colour is evaluated there instead of from rows re-read from HBM, the gradients of the
+// 11 geometry parameters are read once, and four to five launches become one.  The same functions -- and sh_color /
+// project_fwd_core -- on the same values: bit-identical to the unfused sequence.  It can only start when the
+// geometry all-reduce has landed -- which on a node is exactly what the chunked SH Adam hides under -- so the host
+// selects it by world size (parallel.GradSync.fused_tail).
 struct ChunkTable {
   int n;
   int begin[9];              // row chunk c = [begin[c], begin[c + 1]); multiples of 256 except the last end
@@ -1195,7 +1096,6 @@ __global__ __launch_bounds__(256) void k_adam_sh_geom_next(
     long long capacity, int32_t* __restrict__ sticky, int32_t* __restrict__ tag, int32_t tag_value) {
   if (ad_in.guard && ad_in.guard[1]) return;   // a rank's frame overflowed: no update, the tag keeps its old value
   const AdamK ad = adam_resolve(ad_in);
-  constexpr int K = (DEG + 1) * (DEG + 1);
   const int ROW = 3 * sh_stride, RS = ROW + 4, F4 = ROW / 4;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
@@ -1211,104 +1111,22 @@ __global__ __launch_bounds__(256) void k_adam_sh_geom_next(
     if (c < ct.n && g0 >= ct.begin[c] && g0 < ct.begin[c + 1]) { row0 = ct.begin[c]; rows_c = ct.begin[c + 1] - ct.begin[c]; v_color_all = ct.blk[c]; }
   float m[3] = {0.f, 0.f, 0.f}, ls[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f};
   float ol = 0.f;
-  // ---- the SH gradient sum_r Y(dir_r) (x) v_color_r of this row, in rank order, into the LDS image (k_adam_sh_gathered) ----
+  // ---- the SH gradient sum_r Y(dir_r) (x) v_color_r of this row, in rank order, into the LDS image ----
   if (g < N) {
     m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];   // the means the forward pass used
-    float acc[3 * K];
-#pragma unroll
-    for (int i = 0; i < 3 * K; i++) acc[i] = 0.f;
-    const size_t nb = (size_t)rows_c;
-    const size_t blk_r = 3 * nb + 4;
-    for (int r = 0; r < world; r++) {
-      const float* vc = v_color_all + r * blk_r + 3 * (size_t)(g - row0);
-      const float* cp = v_color_all + r * blk_r + 3 * nb;
-      const float v0 = vc[0], v1 = vc[1], v2 = vc[2];
-      const float dx = m[0] - cp[0], dy = m[1] - cp[1], dz = m[2] - cp[2];
-      const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-      float Y[16];
-      sh_basis<DEG>(dx * inv, dy * inv, dz * inv, Y);
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-        acc[3 * k] = fmaf(Y[k], v0, acc[3 * k]);
-        acc[3 * k + 1] = fmaf(Y[k], v1, acc[3 * k + 1]);
-        acc[3 * k + 2] = fmaf(Y[k], v2, acc[3 * k + 2]);
-      }
-    }
-    float* row = lds + tid * RS;
-#pragma unroll
-    for (int i = 0; i < 3 * K / 4; i++) st4(row + 4 * i, make_float4(acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]));
-    if constexpr ((3 * K) % 4 != 0) {
-      float t[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < (3 * K) % 4; i++) t[i] = acc[(3 * K / 4) * 4 + i];
-      st4(row + (3 * K / 4) * 4, make_float4(t[0], t[1], t[2], t[3]));
-    }
-    for (int i = (3 * K + 3) / 4; i < F4; i++) st4(row + 4 * i, make_float4(0.f, 0.f, 0.f, 0.f));
+    sh_grad_gathered<DEG>(world, v_color_all, (size_t)rows_c, g - row0, m[0], m[1], m[2], lds + tid * RS, F4);
   }
   __syncthreads();
   // ---- Adam over the block's SH rows; the updated coefficients replace the consumed gradient in the image ----
-  const int nf = nrows * F4;
-  for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
-    float4 P[2], M[2], V[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int f = f0 + 256 * u;
-      if (f < nf) {
-        const size_t e = blk + 4 * (size_t)f;
-        P[u] = ld4_nt(sh + e); M[u] = ld4_nt(exp_avg + ad.e_opac + e); V[u] = ld4_nt(exp_avg_sq + ad.e_opac + e);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-      const int f = f0 + 256 * u;
-      if (f < nf) {
-        const int row = f / F4, c4 = f - row * F4;
-        const float4 G = ld4(lds + row * RS + 4 * c4);
-        const size_t e = blk + 4 * (size_t)f;
-        const int c = 4 * c4;
-        adam1(ad, c < 3 ? ad.lr_dc : ad.lr_rest, P[u].x, G.x, M[u].x, V[u].x);
-        adam1(ad, c + 1 < 3 ? ad.lr_dc : ad.lr_rest, P[u].y, G.y, M[u].y, V[u].y);
-        adam1(ad, c + 2 < 3 ? ad.lr_dc : ad.lr_rest, P[u].z, G.z, M[u].z, V[u].z);
-        adam1(ad, ad.lr_rest, P[u].w, G.w, M[u].w, V[u].w);
-        st4_nt(sh + e, P[u]); st4_nt(exp_avg + ad.e_opac + e, M[u]); st4_nt(exp_avg_sq + ad.e_opac + e, V[u]);
-        st4(lds + row * RS + 4 * c4, P[u]);
-      }
-    }
-  }
+  adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, blk, nrows, F4, RS, tid, true);
   __syncthreads();
-  // ---- Adam on the 11 geometry parameters (k_adam_geom_project_next), then the next camera's colour from the LDS row ----
+  // ---- Adam on the 11 geometry parameters, then the next camera's colour from the LDS row ----
   if (g < N) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const long long e = 3ll * g + j;
-      float P = m[j], M = exp_avg[e], V = exp_avg_sq[e];
-      adam1(ad, ad.lr_means, P, grads[e], M, V);
-      means[3 * g + j] = P; exp_avg[e] = M; exp_avg_sq[e] = V;
-      m[j] = P;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const long long e = ad.e_means + 3ll * g + j;
-      float P = log_scales[3 * g + j], M = exp_avg[e], V = exp_avg_sq[e];
-      adam1(ad, ad.lr_scales, P, grads[e], M, V);
-      log_scales[3 * g + j] = P; exp_avg[e] = M; exp_avg_sq[e] = V;
-      ls[j] = P;
-    }
-    {
-      const long long e = ad.e_scales + 4ll * g;
-      float4 Q = ld4(quats + 4 * (size_t)g), G = ld4_nt(grads + e), M = ld4_nt(exp_avg + e), V = ld4_nt(exp_avg_sq + e);
-      adam1(ad, ad.lr_quats, Q.x, G.x, M.x, V.x); adam1(ad, ad.lr_quats, Q.y, G.y, M.y, V.y);
-      adam1(ad, ad.lr_quats, Q.z, G.z, M.z, V.z); adam1(ad, ad.lr_quats, Q.w, G.w, M.w, V.w);
-      st4(quats + 4 * (size_t)g, Q); st4_nt(exp_avg + e, M); st4_nt(exp_avg_sq + e, V);
-      q[0] = Q.x; q[1] = Q.y; q[2] = Q.z; q[3] = Q.w;
-    }
-    {
-      const long long e = ad.e_quats + g;
-      float P = opac_logit[g], M = exp_avg[e], V = exp_avg_sq[e];
-      adam1(ad, ad.lr_opac, P, grads[e], M, V);
-      opac_logit[g] = P; exp_avg[e] = M; exp_avg_sq[e] = V;
-      ol = P;
-    }
+    ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
+    const float4 q4 = ld4(quats + 4 * (size_t)g);
+    q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+    ol = opac_logit[g];
+    adam_geom_flat(ad, g, m, ls, q, ol, grads, means, log_scales, quats, opac_logit, exp_avg, exp_avg_sq);
     sh_color<DEG>(m, cam.campos, lds + tid * RS, rgb);
   }
   __syncthreads();     // the group scan of K1 takes over the SH image
@@ -1351,6 +1169,10 @@ __global__ __launch_bounds__(256) void k_sh_op(int N, int sh_stride, const float
 inline bool lds_k8_ok(int sh_deg, int sh_stride) {
   return (sh_stride == 16 && sh_deg >= 0 && sh_deg <= 3) || (sh_stride == 4 && sh_deg >= 0 && sh_deg <= 1);
 }
+#define DISPATCH_DEG(M, deg)                                                                     \
+  do {                                                                                           \
+    switch (deg) { case 0: M(0); break; case 1: M(1); break; case 2: M(2); break; default: M(3); break; } \
+  } while (0)
 #define DISPATCH_DEG_KS(M, deg, ks)                                                              \
   do {                                                                                           \
     if ((ks) == 16) {                                                                            \
@@ -1520,8 +1342,34 @@ extern "C" int tgs_project_bwd_adam_next(const TgsCamera* cam, int N, int sh_str
                                group_base, partials, v_xy, skip_if_overflow, nx, stream);
 }
 
-// Fused K8 + Adam + the next view's colours AND its K1 (front prefetch).  The next frame's counters are cleared
-// here, before the kernel that counts into them; tgs_project_bin_sort_front finishes that frame.
+// What the three entry points that run the NEXT view's K1 inside an optimizer kernel share once they have checked their
+// arguments (each checks in its own order and in its own name, `fn` here): the next frame's counters are cleared, before
+// the kernel that counts into them, and `fr` receives the kernel's view of that frame.
+static int next_front_begin(const char* fn, const TgsCamera* next_cam, float* splats_next, int32_t* radii_next,
+                            int32_t* group_base_next, int32_t* tile_cursor_next, int64_t capacity_next,
+                            void* scratch_next, int32_t* status_next, int32_t* sticky_overflow, int counters_cleared,
+                            hipStream_t s, NextFront* fr) {
+  fr->cam = make_camk(next_cam);
+  fr->splats = splats_next; fr->radii = radii_next; fr->group_base = group_base_next;
+  fr->tile_count = tile_cursor_next; fr->rank = carve_scratch(scratch_next, capacity_next).rank;
+  fr->status = status_next; fr->capacity = (long long)capacity_next; fr->sticky = sticky_overflow;
+  if (!counters_cleared) {
+    const int T = fr->cam.TW * fr->cam.TH;
+    hipLaunchKernelGGL(k_clear_counters, dim3((max(TGS_XCC * T, 2) + 255) / 256), dim3(256), 0, s, tile_cursor_next, T,
+                       status_next, sticky_overflow);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      tgs_set_error("%s: HIP launch failed: %s", fn, hipGetErrorString(e));
+      return TGS_E_HIP;
+    }
+  }
+  return TGS_OK;
+}
+// the front arguments of a kernel that takes them one by one
+#define NEXT_FRONT_ARGS(fr) \
+  (fr).splats, (fr).radii, (fr).group_base, (fr).tile_count, (fr).rank, (fr).status, (fr).capacity, (fr).sticky
+
+// Fused K8 + Adam + the next view's colours AND its K1 (front prefetch); tgs_project_bin_sort_front finishes that frame.
 extern "C" int tgs_project_bwd_adam_next_front(const TgsCamera* cam, int N, int sh_stride, int sh_deg,
                                                float* params, float* exp_avg, float* exp_avg_sq,
                                                const TgsAdamSpec* spec, const float* splats,
@@ -1540,20 +1388,12 @@ extern "C" int tgs_project_bwd_adam_next_front(const TgsCamera* cam, int N, int 
   TGS_CHECK_ARG(splats_next && group_base_next && tile_cursor_next && scratch_next && status_next, "null front buffer");
   TGS_CHECK_ARG(capacity_next >= 0 && capacity_next < (1ll << 31), "bad capacity");
   if (N <= 0) return TGS_OK;
-  const CamK kn = make_camk(next_cam);
-  const int T = kn.TW * kn.TH;
-  const BinScratch sc = carve_scratch(scratch_next, capacity_next);
-  if (!counters_cleared) {
-    hipLaunchKernelGGL(k_clear_counters, dim3((max(TGS_XCC * T, 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       tile_cursor_next, T, status_next, sticky_overflow);
-    TGS_CHECK_LAUNCH();
-  }
   NextView nx;
-  nx.campos[0] = kn.campos[0]; nx.campos[1] = kn.campos[1]; nx.campos[2] = kn.campos[2];
+  if (const int rc = next_front_begin(__func__, next_cam, splats_next, radii_next, group_base_next, tile_cursor_next,
+                                      capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared,
+                                      (hipStream_t)stream, &nx.fr)) return rc;
+  nx.campos[0] = nx.fr.cam.campos[0]; nx.campos[1] = nx.fr.cam.campos[1]; nx.campos[2] = nx.fr.cam.campos[2];
   nx.colors = colors_next; nx.tag = tag_word; nx.tag_value = tag_value;
-  nx.fr.cam = kn; nx.fr.splats = splats_next; nx.fr.radii = radii_next; nx.fr.group_base = group_base_next;
-  nx.fr.tile_count = tile_cursor_next; nx.fr.rank = sc.rank; nx.fr.status = status_next;
-  nx.fr.capacity = (long long)capacity_next; nx.fr.sticky = sticky_overflow;
   return project_bwd_adam_impl(cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
                                group_base, partials, v_xy, skip_if_overflow, nx, stream);
 }
@@ -1574,15 +1414,11 @@ extern "C" int tgs_adam_geom_project_next(const TgsCamera* next_cam, int N, int 
   TGS_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && spec && tag_word, "null pointer");
   TGS_CHECK_ARG(splats_next && group_base_next && tile_cursor_next && scratch_next && status_next, "null front buffer");
   TGS_CHECK_ARG(sh_deg >= 0 && sh_deg <= 3 && sh_stride >= (sh_deg + 1) * (sh_deg + 1), "bad SH degree / stride");
-  const CamK kn = make_camk(next_cam);
-  const int T = kn.TW * kn.TH;
   hipStream_t s = (hipStream_t)stream;
-  const BinScratch sc = carve_scratch(scratch_next, capacity_next);
-  if (!counters_cleared) {
-    hipLaunchKernelGGL(k_clear_counters, dim3((max(TGS_XCC * T, 2) + 255) / 256), dim3(256), 0, s, tile_cursor_next, T,
-                       status_next, sticky_overflow);
-    TGS_CHECK_LAUNCH();
-  }
+  NextFront fr;
+  if (const int rc = next_front_begin(__func__, next_cam, splats_next, radii_next, group_base_next, tile_cursor_next,
+                                      capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared, s,
+                                      &fr)) return rc;
   AdamK a = make_adamk(N, sh_stride, spec, grad_scale);
   a.guard = skip_if_overflow;
   float* means = params;
@@ -1592,15 +1428,9 @@ extern "C" int tgs_adam_geom_project_next(const TgsCamera* next_cam, int N, int 
   const float* sh = params + a.e_opac;
   const dim3 grid((N + 255) / 256), block(256);
 #define LAUNCH_G(D)                                                                                          \
-  hipLaunchKernelGGL((k_adam_geom_project_next<D>), grid, block, 0, s, kn, N, sh_stride, means, log_scales,    \
-                     quats, opac, sh, grads, a, exp_avg, exp_avg_sq, splats_next, radii_next, group_base_next, \
-                     tile_cursor_next, sc.rank, status_next, (long long)capacity_next, sticky_overflow, tag_word, tag_value)
-  switch (sh_deg) {
-    case 0: LAUNCH_G(0); break;
-    case 1: LAUNCH_G(1); break;
-    case 2: LAUNCH_G(2); break;
-    default: LAUNCH_G(3); break;
-  }
+  hipLaunchKernelGGL((k_adam_geom_project_next<D>), grid, block, 0, s, fr.cam, N, sh_stride, means, log_scales, \
+                     quats, opac, sh, grads, a, exp_avg, exp_avg_sq, NEXT_FRONT_ARGS(fr), tag_word, tag_value)
+  DISPATCH_DEG(LAUNCH_G, sh_deg);
 #undef LAUNCH_G
   TGS_CHECK_LAUNCH();
   return TGS_OK;
@@ -1681,12 +1511,7 @@ static int project_bin_sort_impl(const TgsCamera* cam, int N, const float* means
                      opac_logit, sh, sh_stride, colors_in, splats, radii, group_base, tile_cursor,  \
                      sc.rank, status, (long long)capacity, sticky_overflow, color_tag, tag_expect)
     if (colors_in && color_tag && sh_deg >= 0) {
-      switch (sh_deg) {
-        case 0: LAUNCH_PRE(0); break;
-        case 1: LAUNCH_PRE(1); break;
-        case 2: LAUNCH_PRE(2); break;
-        default: LAUNCH_PRE(3); break;
-      }
+      DISPATCH_DEG(LAUNCH_PRE, sh_deg);
     } else {
       switch (sh_deg) {
         case 0: LAUNCH(0); break;
@@ -1740,12 +1565,9 @@ extern "C" int tgs_sh_fwd(int N, int sh_deg, int sh_stride, const float* dirs, c
   TGS_CHECK_ARG(dirs && coeffs && colors, "null pointer");
   const dim3 grid((N + 255) / 256), block(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (sh_deg) {
-    case 0: hipLaunchKernelGGL((k_sh_op<0, false>), grid, block, 0, s, N, sh_stride, dirs, coeffs, colors); break;
-    case 1: hipLaunchKernelGGL((k_sh_op<1, false>), grid, block, 0, s, N, sh_stride, dirs, coeffs, colors); break;
-    case 2: hipLaunchKernelGGL((k_sh_op<2, false>), grid, block, 0, s, N, sh_stride, dirs, coeffs, colors); break;
-    default: hipLaunchKernelGGL((k_sh_op<3, false>), grid, block, 0, s, N, sh_stride, dirs, coeffs, colors); break;
-  }
+#define LAUNCH(D) hipLaunchKernelGGL((k_sh_op<D, false>), grid, block, 0, s, N, sh_stride, dirs, coeffs, colors)
+  DISPATCH_DEG(LAUNCH, sh_deg);
+#undef LAUNCH
   TGS_CHECK_LAUNCH();
   return TGS_OK;
 }
@@ -1758,12 +1580,9 @@ extern "C" int tgs_sh_bwd(int N, int sh_deg, int sh_stride, const float* dirs, c
   TGS_CHECK_ARG(dirs && v_colors && v_coeffs, "null pointer");
   const dim3 grid((N + 255) / 256), block(256);
   hipStream_t s = (hipStream_t)stream;
-  switch (sh_deg) {
-    case 0: hipLaunchKernelGGL((k_sh_op<0, true>), grid, block, 0, s, N, sh_stride, dirs, v_colors, v_coeffs); break;
-    case 1: hipLaunchKernelGGL((k_sh_op<1, true>), grid, block, 0, s, N, sh_stride, dirs, v_colors, v_coeffs); break;
-    case 2: hipLaunchKernelGGL((k_sh_op<2, true>), grid, block, 0, s, N, sh_stride, dirs, v_colors, v_coeffs); break;
-    default: hipLaunchKernelGGL((k_sh_op<3, true>), grid, block, 0, s, N, sh_stride, dirs, v_colors, v_coeffs); break;
-  }
+#define LAUNCH(D) hipLaunchKernelGGL((k_sh_op<D, true>), grid, block, 0, s, N, sh_stride, dirs, v_colors, v_coeffs)
+  DISPATCH_DEG(LAUNCH, sh_deg);
+#undef LAUNCH
   TGS_CHECK_LAUNCH();
   return TGS_OK;
 }
@@ -1806,12 +1625,7 @@ extern "C" int tgs_project_bwd_color(const TgsCamera* cam, int N, const float* m
                      opac_logit, sh, sh_stride, splats, group_base, partials,                    \
                      (const float*)nullptr, v_means, v_log_scales, v_quats, v_opac_logit,        \
                      (float*)nullptr, v_color, v_xy, skip_if_overflow)
-  switch (sh_deg) {
-    case 0: LAUNCH(0); break;
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    default: LAUNCH(3); break;
-  }
+  DISPATCH_DEG(LAUNCH, sh_deg);
 #undef LAUNCH
   TGS_CHECK_LAUNCH();
   return TGS_OK;
@@ -1887,12 +1701,7 @@ extern "C" int tgs_adam_step_sh_gathered_rows(int world, int N, int row_begin, i
 #define LAUNCH_G(D)                                                                              \
   hipLaunchKernelGGL((k_adam_sh_gathered<D>), grid, block, lds_bytes, s, world, row_begin, row_end, sh_stride, \
                      params, params + a.e_opac, v_color_rows_all, a, exp_avg, exp_avg_sq)
-  switch (sh_deg) {
-    case 0: LAUNCH_G(0); break;
-    case 1: LAUNCH_G(1); break;
-    case 2: LAUNCH_G(2); break;
-    default: LAUNCH_G(3); break;
-  }
+  DISPATCH_DEG(LAUNCH_G, sh_deg);
 #undef LAUNCH_G
   TGS_CHECK_LAUNCH();
   return TGS_OK;
@@ -1936,30 +1745,20 @@ extern "C" int tgs_adam_sh_gathered_geom_project_next(
   for (int c = 0; c < n_chunks; c++) {
     TGS_CHECK_ARG(ct.begin[c] % TGS_GROUP == 0 && ct.begin[c] < ct.begin[c + 1] && ct.blk[c], "bad row chunk");
   }
-  const CamK kn = make_camk(next_cam);
-  const int T = kn.TW * kn.TH;
   hipStream_t s = (hipStream_t)stream;
-  const BinScratch sc = carve_scratch(scratch_next, capacity_next);
-  if (!counters_cleared) {
-    hipLaunchKernelGGL(k_clear_counters, dim3((max(TGS_XCC * T, 2) + 255) / 256), dim3(256), 0, s, tile_cursor_next, T,
-                       status_next, sticky_overflow);
-    TGS_CHECK_LAUNCH();
-  }
+  NextFront fr;
+  if (const int rc = next_front_begin(__func__, next_cam, splats_next, radii_next, group_base_next, tile_cursor_next,
+                                      capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared, s,
+                                      &fr)) return rc;
   AdamK a = make_adamk(N, sh_stride, spec, grad_scale);
   a.guard = skip_if_overflow;
   const dim3 grid((N + 255) / 256), block(256);
   const size_t lds_bytes = 256 * (size_t)(3 * sh_stride + 4) * sizeof(float);
 #define LAUNCH_T(D)                                                                                            \
-  hipLaunchKernelGGL((k_adam_sh_geom_next<D>), grid, block, lds_bytes, s, kn, world, N, sh_stride, params,       \
+  hipLaunchKernelGGL((k_adam_sh_geom_next<D>), grid, block, lds_bytes, s, fr.cam, world, N, sh_stride, params,   \
                      params + a.e_means, params + a.e_scales, params + a.e_quats, params + a.e_opac, grads, ct, a, \
-                     exp_avg, exp_avg_sq, splats_next, radii_next, group_base_next, tile_cursor_next, sc.rank,     \
-                     status_next, (long long)capacity_next, sticky_overflow, tag_word, tag_value)
-  switch (sh_deg) {
-    case 0: LAUNCH_T(0); break;
-    case 1: LAUNCH_T(1); break;
-    case 2: LAUNCH_T(2); break;
-    default: LAUNCH_T(3); break;
-  }
+                     exp_avg, exp_avg_sq, NEXT_FRONT_ARGS(fr), tag_word, tag_value)
+  DISPATCH_DEG(LAUNCH_T, sh_deg);
 #undef LAUNCH_T
   TGS_CHECK_LAUNCH();
   return TGS_OK;

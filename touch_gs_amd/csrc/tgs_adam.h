@@ -1,4 +1,5 @@
-// tgs_adam.h -- Adam update shared by K9 (optim.hip) and the fused K8+Adam kernel (project.hip).
+// tgs_adam.h -- the Adam update (adam1) shared by K9 (optim.hip) and the optimizer kernels of project.hip, and the two
+// traversals those four kernels share: adam_sh_stream (SH rows through an LDS image) and adam_geom (the other 11).
 #pragma once
 #include <math.h>
 #include "tgs_common.h"
@@ -59,5 +60,94 @@ __device__ __forceinline__ void adam1(const AdamK& a, float lr, float& p, float 
   v = fmaf(a.b2, v, ((1.f - a.b2) * g) * g);
   const float denom = fmaf(sqrtf(v), a.isq_bc2, a.eps);
   p -= (lr * (m * a.ibc1)) / denom;
+}
+
+// Adam on the SH rows of a workgroup's `nrows` consecutive Gaussians, whose gradients sit in the LDS image
+// lds[row * RS + column] (F4 float4 columns per row): the block [blk, blk + nrows * 4 F4) of sh and of both moments is
+// streamed fully coalesced, 2 float4 columns per thread and round so that 6 independent loads are in flight.
+// keep: the updated coefficients replace the consumed gradient in the image (for a colour evaluation that follows).
+// The ONE body of the fused K8+Adam kernel, k_adam_sh_gathered and k_adam_sh_geom_next (project.hip).
+__device__ __forceinline__ void adam_sh_stream(const AdamK& ad, float* sh, float* exp_avg, float* exp_avg_sq, float* lds,
+                                               size_t blk, int nrows, int F4, int RS, int tid, bool keep) {
+  const int nf = nrows * F4;
+  for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
+    float4 P[2], M[2], V[2];
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int f = f0 + 256 * u;
+      if (f < nf) {
+        const size_t e = blk + 4 * (size_t)f;
+        P[u] = ld4_nt(sh + e); M[u] = ld4_nt(exp_avg + ad.e_opac + e); V[u] = ld4_nt(exp_avg_sq + ad.e_opac + e);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int f = f0 + 256 * u;
+      if (f < nf) {
+        const int row = f / F4, c4 = f - row * F4;
+        const float4 G = ld4(lds + row * RS + 4 * c4);
+        const size_t e = blk + 4 * (size_t)f;
+        const int c = 4 * c4;  // column of the first element inside the 3K-float row; DC = columns 0..2
+        adam1(ad, c < 3 ? ad.lr_dc : ad.lr_rest, P[u].x, G.x, M[u].x, V[u].x);
+        adam1(ad, c + 1 < 3 ? ad.lr_dc : ad.lr_rest, P[u].y, G.y, M[u].y, V[u].y);
+        adam1(ad, c + 2 < 3 ? ad.lr_dc : ad.lr_rest, P[u].z, G.z, M[u].z, V[u].z);
+        adam1(ad, ad.lr_rest, P[u].w, G.w, M[u].w, V[u].w);
+        st4_nt(sh + e, P[u]); st4_nt(exp_avg + ad.e_opac + e, M[u]); st4_nt(exp_avg_sq + ad.e_opac + e, V[u]);
+        if (keep) st4(lds + row * RS + 4 * c4, P[u]);
+      }
+    }
+  }
+}
+
+// Adam on the 11 non-SH parameters of Gaussian g by its owner thread.  Parameters (m, ls, q, ol) and gradients
+// (gm, gls, gq, go) come in registers; the moments are read and written here (flat-buffer offsets from the layout),
+// the parameters are stored and their updated values stay in m / ls / q / ol for the caller's colour evaluation and K1.
+// NT_Q: cache hint of the quaternion store (the callers differ; measured per kernel, not unified here).
+template <bool NT_Q>
+__device__ __forceinline__ void adam_geom(const AdamK& ad, int g, float* m, float* ls, float* q, float& ol,
+                                          const float* gm, const float* gls, const float* gq, float go,
+                                          float* means, float* log_scales, float* quats, float* opac_logit,
+                                          float* exp_avg, float* exp_avg_sq) {
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const long long e = 3ll * g + j;
+    float M = exp_avg[e], V = exp_avg_sq[e];
+    adam1(ad, ad.lr_means, m[j], gm[j], M, V);
+    means[3 * g + j] = m[j]; exp_avg[e] = M; exp_avg_sq[e] = V;
+  }
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const long long e = ad.e_means + 3ll * g + j;
+    float M = exp_avg[e], V = exp_avg_sq[e];
+    adam1(ad, ad.lr_scales, ls[j], gls[j], M, V);
+    log_scales[3 * g + j] = ls[j]; exp_avg[e] = M; exp_avg_sq[e] = V;
+  }
+  {
+    const long long e = ad.e_scales + 4ll * g;
+    float4 M = ld4_nt(exp_avg + e), V = ld4_nt(exp_avg_sq + e);
+    adam1(ad, ad.lr_quats, q[0], gq[0], M.x, V.x); adam1(ad, ad.lr_quats, q[1], gq[1], M.y, V.y);
+    adam1(ad, ad.lr_quats, q[2], gq[2], M.z, V.z); adam1(ad, ad.lr_quats, q[3], gq[3], M.w, V.w);
+    const float4 Q = make_float4(q[0], q[1], q[2], q[3]);
+    if constexpr (NT_Q) st4_nt(quats + 4 * (size_t)g, Q); else st4(quats + 4 * (size_t)g, Q);
+    st4_nt(exp_avg + e, M); st4_nt(exp_avg_sq + e, V);
+  }
+  {
+    const long long e = ad.e_quats + g;
+    float M = exp_avg[e], V = exp_avg_sq[e];
+    adam1(ad, ad.lr_opac, ol, go, M, V);
+    opac_logit[g] = ol; exp_avg[e] = M; exp_avg_sq[e] = V;
+  }
+}
+
+// The same with the gradients read from the flat (all-reduced) gradient buffer, which has the parameters' layout.
+__device__ __forceinline__ void adam_geom_flat(const AdamK& ad, int g, float* m, float* ls, float* q, float& ol,
+                                               const float* grads, float* means, float* log_scales, float* quats,
+                                               float* opac_logit, float* exp_avg, float* exp_avg_sq) {
+  const float gm[3] = {grads[3ll * g], grads[3ll * g + 1], grads[3ll * g + 2]};
+  const float gls[3] = {grads[ad.e_means + 3ll * g], grads[ad.e_means + 3ll * g + 1], grads[ad.e_means + 3ll * g + 2]};
+  const float4 G = ld4_nt(grads + ad.e_scales + 4ll * g);
+  const float gq[4] = {G.x, G.y, G.z, G.w};
+  adam_geom<false>(ad, g, m, ls, q, ol, gm, gls, gq, grads[ad.e_quats + g], means, log_scales, quats, opac_logit,
+                   exp_avg, exp_avg_sq);
 }
 #endif
