@@ -22,7 +22,7 @@ import torch
 
 from oracle import torch_oracle as O
 from tests.depth_stats_ref import clear_pixels, depth_stats_ref
-from tests.util import amd_cam, splat_fields, to_dev
+from tests.util import amd_cam, clamp_scene, count_clamped, splat_fields, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -161,6 +161,47 @@ def test_outputs_do_not_depend_on_stop_pos_schedule_or_kernel_form(dev):
         assert torch.equal(depth_q, depth) and torch.equal(fT_q, fT) and torch.equal(fT_q.stop_pos, fT.stop_pos)
         same(ops.rasterize_depth_stats(cam, sp, sg, ts, depth_q, fT_q, want_gid=True, opts=ops.raster_opts(k6_blocks=0)),
              "quadrant-form forward")
+
+
+def test_clamped_entries_walk_the_same_in_every_form(dev):
+    """Batches with an opacity above 0.99 take the walk's copy WITH the 0.999 clamp (MAYCLAMP = true), which no other
+    scene of this module reaches.  On the ragged clamp scene of test_k6_block_form_is_bit_identical the three images are
+    bit-identical unsplit and with every tile of the schedule's head in quadrant blocks, with the forward's stop positions
+    and without, and from a quadrant-form forward's images; a pixel has a median exactly where it ends with T <= 1/2."""
+    from touch_gs_amd import ops
+    N, W, H, deg = 3000, 100, 70, 1
+    P, ocam = clamp_scene(N, W, H, deg, 79)
+    acam = amd_cam(ocam)
+    sp, gb, ts, sg = _front(dev, to_dev(P, dev), acam, deg)
+    T = acam.num_tiles
+    n = int(ts[T])
+    assert count_clamped(splat_fields(sp), sg[:n].cpu().numpy(), ts.cpu().numpy(), ocam) > 0
+    assert int((ts[1:T + 1] - ts[:T]).max()) > 64                 # (tiles that the floor-64 rule below really splits)
+    assert ts.tile_order is not None                              # (no split without the schedule)
+    unsplit = ops.raster_opts(k6_split=0)
+    split = ops.raster_opts(k6_split=1, k6_split_floor=64, k6_split_heads=4096)
+    rgb, depth, fT, _ = ops.rasterize_fwd(acam, sp, sg, ts, opts=unsplit)
+    assert fT.stop_pos is not None
+    fT_plain = fT.clone()                                         # (a copy does not carry .stop_pos)
+    assert getattr(fT_plain, "stop_pos", None) is None
+    base = ops.rasterize_depth_stats(acam, sp, sg, ts, depth, fT, want_gid=True, opts=unsplit)
+
+    def same(got, why):
+        for name, a, b in zip(("depth_var", "median_depth", "median_gid"), base, got):
+            assert torch.equal(a, b), (why, name)
+
+    for name, opts in (("unsplit", unsplit), ("split", split)):
+        for f in (fT, fT_plain):
+            same(ops.rasterize_depth_stats(acam, sp, sg, ts, depth, f, want_gid=True, opts=opts),
+                 (name, "stop_pos" if f is fT else "stop_pos=None"))
+    rgb_q, depth_q, fT_q, _ = ops.rasterize_fwd(acam, sp, sg, ts, opts=ops.raster_opts(k6_blocks=0))
+    assert torch.equal(depth_q, depth) and torch.equal(fT_q, fT) and torch.equal(fT_q.stop_pos, fT.stop_pos)
+    for name, opts in (("unsplit", unsplit), ("split", split)):
+        same(ops.rasterize_depth_stats(acam, sp, sg, ts, depth_q, fT_q, want_gid=True, opts=opts), ("quadrant-form forward", name))
+    var, med, gid = base
+    assert torch.equal(gid >= 0, fT <= 0.5)
+    assert bool((gid >= 0).any())
+    assert bool((var >= 0).all())
 
 
 def test_pass_leaves_the_scratch_behind_tile_start_and_the_backward_alone(dev):

@@ -148,21 +148,22 @@ __device__ __forceinline__ TileRec make_tile_rec(float4 r0, float4 r1, float4 r2
   return t;
 }
 
-// per-lane pixel constants of slot k
+// per-lane pixel constants of slot k; (lx, ly) = the lane's pixel in the tile's top-left 8x8 quadrant
 struct PixConst {
   float u[2], v[2], uu[2], vv[2], uv[4];
 };
 
-__device__ __forceinline__ PixConst make_pix_const(int lane) {
+__device__ __forceinline__ PixConst make_pix_const(int lx, int ly) {
   PixConst p;
-  p.u[0] = (float)(lane & 7) - 7.5f; p.u[1] = p.u[0] + 8.f;
-  p.v[0] = (float)(lane >> 3) - 7.5f; p.v[1] = p.v[0] + 8.f;
+  p.u[0] = (float)lx - 7.5f; p.u[1] = p.u[0] + 8.f;
+  p.v[0] = (float)ly - 7.5f; p.v[1] = p.v[0] + 8.f;
 #pragma unroll
   for (int i = 0; i < 2; i++) { p.uu[i] = p.u[i] * p.u[i]; p.vv[i] = p.v[i] * p.v[i]; }
 #pragma unroll
   for (int k = 0; k < 4; k++) p.uv[k] = p.u[k & 1] * p.v[k >> 1];
   return p;
 }
+__device__ __forceinline__ PixConst make_pix_const(int lane) { return make_pix_const(lane & 7, lane >> 3); }   // quadrant forms
 
 __device__ __forceinline__ float eval_s(const float4& a, const float4& b, const PixConst& p, int k) {
   float s = fmaf(a.y, p.u[k & 1], a.x);
@@ -440,25 +441,19 @@ typedef std::conditional<BLK_U == 4, unsigned int, std::conditional<BLK_U == 2, 
 // would walk ~1600 entries for 256 pixels walks the ~half of them that reach its quadrant, for 64, while the rest of the
 // GPU -- idle in an object-centric frame, whose longest tile IS the launch -- hosts the other three.  Same
 // staging, same blend_step on the same bits per pixel: images, final_T and stop positions bit for bit those of the other forms.
-template <bool WANT_IDX>
-__device__ __forceinline__ void raster_fwd_quadrant(
-    const CamK& cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
-    const int32_t* __restrict__ tile_start, float* __restrict__ out_rgb, float* __restrict__ out_depth,
-    float* __restrict__ final_T, int32_t* __restrict__ final_idx, int32_t* __restrict__ stop_pos,
-    int tile, int k, float4* __restrict__ recs) {
+// walk_quadrant is that form's list walk over entries [start, end) of tile (tx, ty) -- staging, the scalar bit scan over
+// the entries whose quadrant mask reaches quadrant k, the lane's s -- for the forward and the depth-statistics pass alike;
+// step(s, qb, qc, pos) is the caller's update by the entry at list position pos (relative to `start`): blend_step<true> on
+// its own accumulators and the live / stop word smax, which the walk tests once per batch.
+template <class Step>
+__device__ __forceinline__ void walk_quadrant(const CamK& cam, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+                                              int tx, int ty, int k, int start, int end, const float& smax,
+                                              float4* __restrict__ recs, Step&& step) {
   const int lane = threadIdx.x;
-  const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
   const PixConst pc = make_pix_const(lane);
   const float pu = (k & 1) ? pc.u[1] : pc.u[0], pv = (k >> 1) ? pc.v[1] : pc.v[0];
   const float puu = (k & 1) ? pc.uu[1] : pc.uu[0], pvv = (k >> 1) ? pc.vv[1] : pc.vv[0];
   const float puv = k == 0 ? pc.uv[0] : (k == 1 ? pc.uv[1] : (k == 2 ? pc.uv[2] : pc.uv[3]));
-  const int px = tx * TGS_BLOCK + 8 * (k & 1) + (lane & 7);
-  const int py = ty * TGS_BLOCK + 8 * (k >> 1) + (lane >> 3);
-  const bool inb = px < cam.W && py < cam.H;
-  float smax = inb ? LOG2_255 : -3.0e38f;
-  float T = 1.f, Cr = 0.f, Cg = 0.f, Cb = 0.f, D = 0.f;
-  int last = -1;
-  const int start = tile_start[tile], end = tile_start[tile + 1];
   for (int base = start; base < end; base += 64) {
     if (__ballot(smax > 0.f) == 0ull) break;
     __syncthreads();
@@ -483,16 +478,37 @@ __device__ __forceinline__ void raster_fwd_quadrant(
       s = fmaf(qa.w, puu, s);
       s = fmaf(qb.x, puv, s);
       s = fmaf(qb.y, pvv, s);
-      float Tn; bool go;
-      unsigned long long okb = 0ull;
-      const float al = blend_step<true, 0>(s, T, smax, Tn, go, okb, stop_code(base - start + j));
-      const float w = al * T;
-      Cr = fmaf(w, qb.w, Cr); Cg = fmaf(w, qc.x, Cg);
-      Cb = fmaf(w, qc.y, Cb); D = fmaf(w, qb.z, D);
-      T = go ? Tn : T;
-      if (WANT_IDX) last = go ? (base - start + j) : last;
+      step(s, qb, qc, base - start + j);
     }
   }
+}
+
+template <bool WANT_IDX>
+__device__ __forceinline__ void raster_fwd_quadrant(
+    const CamK& cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+    const int32_t* __restrict__ tile_start, float* __restrict__ out_rgb, float* __restrict__ out_depth,
+    float* __restrict__ final_T, int32_t* __restrict__ final_idx, int32_t* __restrict__ stop_pos,
+    int tile, int k, float4* __restrict__ recs) {
+  const int lane = threadIdx.x;
+  const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
+  const int px = tx * TGS_BLOCK + 8 * (k & 1) + (lane & 7);
+  const int py = ty * TGS_BLOCK + 8 * (k >> 1) + (lane >> 3);
+  const bool inb = px < cam.W && py < cam.H;
+  float smax = inb ? LOG2_255 : -3.0e38f;
+  float T = 1.f, Cr = 0.f, Cg = 0.f, Cb = 0.f, D = 0.f;
+  int last = -1;
+  const int start = tile_start[tile], end = tile_start[tile + 1];
+  walk_quadrant(cam, splats, sorted_gid, tx, ty, k, start, end, smax, recs,
+                [&](float s, const float4& qb, const float4& qc, int pos) {
+                  float Tn; bool go;
+                  unsigned long long okb = 0ull;
+                  const float al = blend_step<true, 0>(s, T, smax, Tn, go, okb, stop_code(pos));
+                  const float w = al * T;
+                  Cr = fmaf(w, qb.w, Cr); Cg = fmaf(w, qc.x, Cg);
+                  Cb = fmaf(w, qc.y, Cb); D = fmaf(w, qb.z, D);
+                  T = go ? Tn : T;
+                  if (WANT_IDX) last = go ? pos : last;
+                });
   if (inb) {
     const size_t p = (size_t)py * cam.W + px;
     out_rgb[3 * p] = Cr + T * cam.bg[0];
@@ -520,53 +536,51 @@ __device__ __forceinline__ bool tile_is_split(int n, int I, SplitRule r) {
   return r.factor > 0 && n > max(r.floor, (int)(((long long)I * r.factor) >> 12));
 }
 
-template <bool WANT_IDX>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVES, 8))) void k_raster_fwd_blocks(
-    CamK cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
-    const int32_t* __restrict__ tile_start, float* __restrict__ out_rgb,
-    float* __restrict__ out_depth, float* __restrict__ final_T, int32_t* __restrict__ final_idx,
-    const int32_t* __restrict__ tile_order, int32_t* __restrict__ stop_pos, SplitRule split) {
-  __shared__ float4 recs[65 * 3];                 // 64 staged Gaussians + the null record (alpha = 0)
+// Which part of which tile this block of the forward's launch shape composites.  false: nothing (a slot past the last tile, or
+// an extra block whose tile is not split).  quadrant = -1: the whole tile, in 4x4-block form; 0..3: that 8x8 quadrant of a
+// split tile (the tile's own block takes quadrant 0, the three extra blocks behind the grid's n_slots the others).
+constexpr int SLOT_IDLE = -2;
+__device__ __forceinline__ int split_slot(const int32_t* __restrict__ tile_start, const int32_t* __restrict__ tile_order,
+                                          int T_total, SplitRule split, int& tile) {
   int slot = blockIdx.x, part = -1;
   if (slot >= split.n_slots) {                    // extra blocks: quadrants 1..3 of the schedule's first `heads` tiles
     const int e = slot - split.n_slots;
     slot = e / 3; part = 1 + (e - 3 * slot);
   }
-  const int tile = tile_order ? tile_order[slot] : xcd_tile(slot, T_total);
-  if (tile >= T_total) return;
+  tile = tile_order ? tile_order[slot] : xcd_tile(slot, T_total);
+  if (tile >= T_total) return SLOT_IDLE;
   if (split.factor > 0) {
     const bool sp = slot < split.heads && tile_is_split(tile_start[tile + 1] - tile_start[tile], tile_start[T_total], split);
-    if (part >= 0 && !sp) return;
-    if (sp) {
-      raster_fwd_quadrant<WANT_IDX>(cam, T_total, splats, sorted_gid, tile_start, out_rgb, out_depth, final_T, final_idx,
-                                    stop_pos, tile, part < 0 ? 0 : part, recs);
-      return;
-    }
+    if (part >= 0 && !sp) return SLOT_IDLE;
+    if (sp) return part < 0 ? 0 : part;
   }
-  const int lane = threadIdx.x;
-  const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
-  // lane -> pixel: DPP row g = lane >> 4 owns block (g & 1, g >> 1) of the quadrant, lane & 15 = pixel in it
-  const int g = lane >> 4, lx = 4 * (g & 1) + (lane & 3), ly = 4 * (g >> 1) + ((lane >> 2) & 3);
-  PixConst pc;
-  pc.u[0] = (float)lx - 7.5f; pc.u[1] = pc.u[0] + 8.f;
-  pc.v[0] = (float)ly - 7.5f; pc.v[1] = pc.v[0] + 8.f;
-#pragma unroll
-  for (int i = 0; i < 2; i++) { pc.uu[i] = pc.u[i] * pc.u[i]; pc.vv[i] = pc.v[i] * pc.v[i]; }
-#pragma unroll
-  for (int k = 0; k < 4; k++) pc.uv[k] = pc.u[k & 1] * pc.v[k >> 1];
-  int pxi[4], pyi[4];
-  float smax[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    pxi[k] = tx * TGS_BLOCK + 8 * (k & 1) + lx;
-    pyi[k] = ty * TGS_BLOCK + 8 * (k >> 1) + ly;
-    smax[k] = ((pxi[k] < cam.W) && (pyi[k] < cam.H)) ? LOG2_255 : -3.0e38f;
-  }
-  float T[4] = {1.f, 1.f, 1.f, 1.f};
-  float Cr[4] = {0.f, 0.f, 0.f, 0.f}, Cg[4] = {0.f, 0.f, 0.f, 0.f}, Cb[4] = {0.f, 0.f, 0.f, 0.f};
-  float D[4] = {0.f, 0.f, 0.f, 0.f};
-  int last[4] = {-1, -1, -1, -1};
+  return -1;
+}
 
+// lane -> pixel (lx, ly) of the tile's top-left quadrant in the 4x4-block forms: DPP row g = lane >> 4 owns block
+// (g & 1, g >> 1) of every quadrant, lane & 15 = pixel in it
+__device__ __forceinline__ void block_form_pixel(int lane, int& lx, int& ly) {
+  const int g = lane >> 4;
+  lx = 4 * (g & 1) + (lane & 3);
+  ly = 4 * (g >> 1) + ((lane >> 2) & 3);
+}
+
+// The list walk of the 4x4-block form over entries [start, end) of tile (tx, ty): live tests, staging, block masks, the 16
+// compacted index lists and the per-row loops over them.  The forward and the depth-statistics pass both call it, so the
+// pass includes exactly the entries the forward included.  What they accumulate stays with the caller:
+//   smax           the caller's live / stop words (blend_step), one per pixel slot; the walk tests them and turns the
+//                  batch-relative stop codes into list positions at the end of every batch
+//   step(mayclamp, k, s, qb, qc, j, rel, stopv)
+//                  update of pixel slot k by the entry the lane's row is at: blend_step<mayclamp> with stopv on the caller's
+//                  accumulators.  j = the entry's index in the batch (64 = null record), rel = the batch's first list
+//                  position relative to `start`
+//   batch_end(k, rel)   the caller's own batch-relative codes of slot k -> final ones
+//   WANT_C         stage and read the record's third float4 (the colours); qc is zero without it
+template <bool WANT_C, class Step, class BatchEnd>
+__device__ __forceinline__ void walk_blocks(const CamK& cam, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+                                            int tx, int ty, int start, int end, const PixConst& pc, float (&smax)[4],
+                                            float4* __restrict__ recs, Step&& step, BatchEnd&& batch_end) {
+  const int lane = threadIdx.x;
   __shared__ unsigned int lists4[16 * 16];        // 16 lists of 64 one-byte indices, padded with 64 = null
   unsigned char* lists = reinterpret_cast<unsigned char*>(lists4);
   if (lane == 0) {
@@ -574,8 +588,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
     recs[64 * 3 + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
     recs[64 * 3 + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  const int start = tile_start[tile], end = tile_start[tile + 1];
   // my row's list in quadrant k: block (2 (k & 1) + (g & 1), 2 (k >> 1) + (g >> 1))
+  const int g = lane >> 4;
   int myblock[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) myblock[k] = 4 * (2 * (k >> 1) + (g >> 1)) + 2 * (k & 1) + (g & 1);
@@ -606,7 +620,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
       float gx, gy;
       centre_rel(q0, q2, tx, ty, cam.pix_center, gx, gy);
       const TileRec t = make_tile_rec<false>(q0, q1, q2, gx, gy);
-      recs[lane * 3] = t.a; recs[lane * 3 + 1] = t.b; recs[lane * 3 + 2] = t.c;
+      recs[lane * 3] = t.a; recs[lane * 3 + 1] = t.b;
+      if (WANT_C) recs[lane * 3 + 2] = t.c;
       my_mask = block_mask16(gx, gy, q1.x, q1.y, q1.z, -__log2f(q0.w)) & live16;
       my_opac = q0.w;
     }
@@ -623,7 +638,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
     }
     __syncthreads();
     auto walk = [&](auto mayclamp) {
-      constexpr bool MAYCLAMP = decltype(mayclamp)::value;
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int b0 = 8 * (k >> 1) + 2 * (k & 1);                 // blocks b0, b0 + 1, b0 + 4, b0 + 5
@@ -634,16 +648,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
 #pragma unroll
           for (int e = 0; e < BLK_U; e++) {
             const int j = (idx4 >> (8 * e)) & 0xffu;               // 64 = null record: s = 3e38, alpha = 0
-            const float4 qa = recs[j * 3], qb = recs[j * 3 + 1], qc = recs[j * 3 + 2];
-            const float s = eval_s(qa, qb, pc, k);
-            float Tn; bool go;
-            unsigned long long okb = 0ull;
-            const float al = blend_step<MAYCLAMP, 0>(s, T[k], smax[k], Tn, go, okb, batch_stop_code(j));
-            const float w = al * T[k];
-            Cr[k] = fmaf(w, qb.w, Cr[k]); Cg[k] = fmaf(w, qc.x, Cg[k]);
-            Cb[k] = fmaf(w, qc.y, Cb[k]); D[k] = fmaf(w, qb.z, D[k]);
-            T[k] = go ? Tn : T[k];          // (fmaf(-al, T, T) instead of the select: no difference, same box)
-            if (WANT_IDX) last[k] = go ? (base - start + j) : last[k];
+            const float4 qa = recs[j * 3], qb = recs[j * 3 + 1];
+            const float4 qc = WANT_C ? recs[j * 3 + 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+            step(mayclamp, k, eval_s(qa, qb, pc, k), qb, qc, j, base - start, batch_stop_code(j));
           }
         }
       }
@@ -653,8 +660,58 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
     if (clampy) walk(std::true_type{}); else walk(std::false_type{});   // 144 -> 139 us at cfg3 (same box)
     // pixels that stopped in this batch: batch-relative code -> list position (4 selects per batch, not per entry)
 #pragma unroll
-    for (int k = 0; k < 4; k++) smax[k] = finish_batch_stop(smax[k], base - start);
+    for (int k = 0; k < 4; k++) {
+      smax[k] = finish_batch_stop(smax[k], base - start);
+      batch_end(k, base - start);
+    }
   }
+}
+
+template <bool WANT_IDX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVES, 8))) void k_raster_fwd_blocks(
+    CamK cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+    const int32_t* __restrict__ tile_start, float* __restrict__ out_rgb,
+    float* __restrict__ out_depth, float* __restrict__ final_T, int32_t* __restrict__ final_idx,
+    const int32_t* __restrict__ tile_order, int32_t* __restrict__ stop_pos, SplitRule split) {
+  __shared__ float4 recs[65 * 3];                 // 64 staged Gaussians + the null record (alpha = 0)
+  int tile;
+  const int quadrant = split_slot(tile_start, tile_order, T_total, split, tile);
+  if (quadrant == SLOT_IDLE) return;
+  if (quadrant >= 0) {
+    raster_fwd_quadrant<WANT_IDX>(cam, T_total, splats, sorted_gid, tile_start, out_rgb, out_depth, final_T, final_idx,
+                                  stop_pos, tile, quadrant, recs);
+    return;
+  }
+  const int lane = threadIdx.x;
+  const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
+  int lx, ly;
+  block_form_pixel(lane, lx, ly);
+  const PixConst pc = make_pix_const(lx, ly);
+  int pxi[4], pyi[4];
+  float smax[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    pxi[k] = tx * TGS_BLOCK + 8 * (k & 1) + lx;
+    pyi[k] = ty * TGS_BLOCK + 8 * (k >> 1) + ly;
+    smax[k] = ((pxi[k] < cam.W) && (pyi[k] < cam.H)) ? LOG2_255 : -3.0e38f;
+  }
+  float T[4] = {1.f, 1.f, 1.f, 1.f};
+  float Cr[4] = {0.f, 0.f, 0.f, 0.f}, Cg[4] = {0.f, 0.f, 0.f, 0.f}, Cb[4] = {0.f, 0.f, 0.f, 0.f};
+  float D[4] = {0.f, 0.f, 0.f, 0.f};
+  int last[4] = {-1, -1, -1, -1};
+  const int start = tile_start[tile], end = tile_start[tile + 1];
+  walk_blocks<true>(cam, splats, sorted_gid, tx, ty, start, end, pc, smax, recs,
+                    [&](auto mayclamp, int k, float s, const float4& qb, const float4& qc, int j, int rel, float stopv) {
+                      float Tn; bool go;
+                      unsigned long long okb = 0ull;
+                      const float al = blend_step<decltype(mayclamp)::value, 0>(s, T[k], smax[k], Tn, go, okb, stopv);
+                      const float w = al * T[k];
+                      Cr[k] = fmaf(w, qb.w, Cr[k]); Cg[k] = fmaf(w, qc.x, Cg[k]);
+                      Cb[k] = fmaf(w, qc.y, Cb[k]); D[k] = fmaf(w, qb.z, D[k]);
+                      T[k] = go ? Tn : T[k];          // (fmaf(-al, T, T) instead of the select: no difference, same box)
+                      if (WANT_IDX) last[k] = go ? (rel + j) : last[k];
+                    },
+                    [](int, int) {});
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     if (pxi[k] < cam.W && pyi[k] < cam.H) {
@@ -677,9 +734,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
 // ---------------------------------------------------------------------------------------------
 // K6s depth statistics: per-pixel depth variance and median depth (forward only, after K6)
 // ---------------------------------------------------------------------------------------------
-// A second walk over the lists K6 composited, in K6's launch shape (4x4-block form, long tiles split into quadrant
-// blocks by the same rule), with K6's staging, eval_s and blend_step on the same bits: every pixel includes exactly the
-// entries the forward included, with the same weights w = alpha T.  Two accumulators per pixel instead of five:
+// A second walk over the lists K6 composited, through K6's own code: the launch shape (split_slot), the walks (walk_blocks /
+// walk_quadrant) and blend_step are the forward's, so every pixel includes exactly the entries the forward included, with
+// the same weights w = alpha T.  Two accumulators per pixel instead of five:
 //   V   = sum w (d - Dhat)^2, Dhat = out_depth / max(1 - final_T, 1e-10) from K6's images.  Every term is >= 0 (the
 //         moment form sum w d^2 / alpha - Dhat^2 cancels by up to 1e4 on the oracle's scenes: two digits left in fp32),
 //         and an error of Dhat enters in second order only (sum w (d - Dhat) = 0).
@@ -722,17 +779,13 @@ __device__ __forceinline__ void depth_stats_store(const DepthStatsOut& o, size_t
   if (o.med_gid) o.med_gid[p] = gid;
 }
 
-// one 8x8 quadrant of a long tile, one pixel per lane (the counterpart of raster_fwd_quadrant)
+// one 8x8 quadrant of a long tile, one pixel per lane (the counterpart of raster_fwd_quadrant, on the same walk)
 __device__ __forceinline__ void depth_stats_quadrant(
     const CamK& cam, const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
     const int32_t* __restrict__ tile_start, const float* __restrict__ out_depth, const float* __restrict__ final_T,
     const int32_t* __restrict__ stop_pos, const DepthStatsOut& o, int tile, int k, float4* __restrict__ recs) {
   const int lane = threadIdx.x;
   const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
-  const PixConst pc = make_pix_const(lane);
-  const float pu = (k & 1) ? pc.u[1] : pc.u[0], pv = (k >> 1) ? pc.v[1] : pc.v[0];
-  const float puu = (k & 1) ? pc.uu[1] : pc.uu[0], pvv = (k >> 1) ? pc.vv[1] : pc.vv[0];
-  const float puv = k == 0 ? pc.uv[0] : (k == 1 ? pc.uv[1] : (k == 2 ? pc.uv[2] : pc.uv[3]));
   const int px = tx * TGS_BLOCK + 8 * (k & 1) + (lane & 7);
   const int py = ty * TGS_BLOCK + 8 * (k >> 1) + (lane >> 3);
   const bool inb = px < cam.W && py < cam.H;
@@ -745,33 +798,10 @@ __device__ __forceinline__ void depth_stats_quadrant(
   const int start = tile_start[tile];
   int end = tile_start[tile + 1];
   if (stop_pos) end = start + wave_minmax_i<true>(inb ? min(stop_pos[p], end - start) : 0);
-  for (int base = start; base < end; base += 64) {
-    if (__ballot(smax > 0.f) == 0ull) break;
-    __syncthreads();
-    unsigned my_mask = 0u;
-    if (base + lane < end) {
-      const float* r = splats + (size_t)sorted_gid[base + lane] * TGS_SPLAT_FLOATS;
-      const float4 q0 = ld4(r), q1 = ld4(r + 4), q2 = ld4(r + 8);
-      float gx, gy;
-      centre_rel(q0, q2, tx, ty, cam.pix_center, gx, gy);
-      const TileRec t = make_tile_rec(q0, q1, q2, gx, gy);
-      recs[lane * 3] = t.a; recs[lane * 3 + 1] = t.b; recs[lane * 3 + 2] = t.c;
-      my_mask = __float_as_uint(t.c.w);
-    }
-    __syncthreads();
-    unsigned long long rem = __ballot((my_mask >> k) & 1u);
-    while (rem) {
-      const int j = __builtin_ctzll(rem);
-      rem &= rem - 1;
-      const float4 qa = recs[j * 3], qb = recs[j * 3 + 1];
-      float s = fmaf(qa.y, pu, qa.x);          // eval_s for slot k
-      s = fmaf(qa.z, pv, s);
-      s = fmaf(qa.w, puu, s);
-      s = fmaf(qb.x, puv, s);
-      s = fmaf(qb.y, pvv, s);
-      depth_stats_step<true>(s, qb.z, ~(base - start + j), stop_code(base - start + j), Dhat, T, smax, V, med);
-    }
-  }
+  walk_quadrant(cam, splats, sorted_gid, tx, ty, k, start, end, smax, recs,
+                [&](float s, const float4& qb, const float4&, int pos) {
+                  depth_stats_step<true>(s, qb.z, ~pos, stop_code(pos), Dhat, T, smax, V, med);
+                });
   if (inb) depth_stats_store(o, p, V, fT, T, med, start, splats, sorted_gid);
 }
 
@@ -780,32 +810,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
     const int32_t* __restrict__ tile_start, const float* __restrict__ out_depth, const float* __restrict__ final_T,
     const int32_t* __restrict__ stop_pos, DepthStatsOut o, const int32_t* __restrict__ tile_order, SplitRule split) {
   __shared__ float4 recs[65 * 3];                 // 64 staged Gaussians + the null record (alpha = 0)
-  int slot = blockIdx.x, part = -1;
-  if (slot >= split.n_slots) {                    // extra blocks: quadrants 1..3 of the schedule's first `heads` tiles
-    const int e = slot - split.n_slots;
-    slot = e / 3; part = 1 + (e - 3 * slot);
-  }
-  const int tile = tile_order ? tile_order[slot] : xcd_tile(slot, T_total);
-  if (tile >= T_total) return;
-  if (split.factor > 0) {
-    const bool sp = slot < split.heads && tile_is_split(tile_start[tile + 1] - tile_start[tile], tile_start[T_total], split);
-    if (part >= 0 && !sp) return;
-    if (sp) {
-      depth_stats_quadrant(cam, splats, sorted_gid, tile_start, out_depth, final_T, stop_pos, o, tile, part < 0 ? 0 : part, recs);
-      return;
-    }
+  int tile;
+  const int quadrant = split_slot(tile_start, tile_order, T_total, split, tile);
+  if (quadrant == SLOT_IDLE) return;
+  if (quadrant >= 0) {
+    depth_stats_quadrant(cam, splats, sorted_gid, tile_start, out_depth, final_T, stop_pos, o, tile, quadrant, recs);
+    return;
   }
   const int lane = threadIdx.x;
   const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
-  // lane -> pixel as in k_raster_fwd_blocks: DPP row g owns block (g & 1, g >> 1) of the quadrant
-  const int g = lane >> 4, lx = 4 * (g & 1) + (lane & 3), ly = 4 * (g >> 1) + ((lane >> 2) & 3);
-  PixConst pc;
-  pc.u[0] = (float)lx - 7.5f; pc.u[1] = pc.u[0] + 8.f;
-  pc.v[0] = (float)ly - 7.5f; pc.v[1] = pc.v[0] + 8.f;
-#pragma unroll
-  for (int i = 0; i < 2; i++) { pc.uu[i] = pc.u[i] * pc.u[i]; pc.vv[i] = pc.v[i] * pc.v[i]; }
-#pragma unroll
-  for (int k = 0; k < 4; k++) pc.uv[k] = pc.u[k & 1] * pc.v[k >> 1];
+  int lx, ly;
+  block_form_pixel(lane, lx, ly);
+  const PixConst pc = make_pix_const(lx, ly);
   const int start = tile_start[tile];
   int end = tile_start[tile + 1];
   bool inb[4];
@@ -826,84 +842,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TGS_BLK_WAVE
   float T[4] = {1.f, 1.f, 1.f, 1.f};
   float V[4] = {0.f, 0.f, 0.f, 0.f};
   int med[4] = {MED_NONE, MED_NONE, MED_NONE, MED_NONE};
-
-  __shared__ unsigned int lists4[16 * 16];        // 16 lists of 64 one-byte indices, padded with 64 = null
-  unsigned char* lists = reinterpret_cast<unsigned char*>(lists4);
-  if (lane == 0) {
-    recs[64 * 3] = make_float4(3.0e38f, 0.f, 0.f, 0.f);
-    recs[64 * 3 + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    recs[64 * 3 + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  int myblock[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) myblock[k] = 4 * (2 * (k >> 1) + (g >> 1)) + 2 * (k & 1) + (g & 1);
-
-  unsigned live16 = 0xffffu;
-  for (int base = start; base < end; base += 64) {
-    unsigned long long lv[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) lv[k] = __ballot(smax[k] > 0.f);
-    if ((lv[0] | lv[1] | lv[2] | lv[3]) == 0ull) break;
-    if ((((base - start) >> 6) & 3) == 0) {
-      live16 = 0u;
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          live16 |= ((lv[k] >> (16 * r)) & 0xffffull) ? (1u << (4 * (2 * (k >> 1) + (r >> 1)) + 2 * (k & 1) + (r & 1))) : 0u;
-    }
-    __syncthreads();
-    unsigned my_mask = 0u;
-    float my_opac = 0.f;
-    if (base + lane < end) {
-      const float* r = splats + (size_t)sorted_gid[base + lane] * TGS_SPLAT_FLOATS;
-      const float4 q0 = ld4(r), q1 = ld4(r + 4), q2 = ld4(r + 8);
-      float gx, gy;
-      centre_rel(q0, q2, tx, ty, cam.pix_center, gx, gy);
-      const TileRec t = make_tile_rec<false>(q0, q1, q2, gx, gy);
-      recs[lane * 3] = t.a; recs[lane * 3 + 1] = t.b;      // (the colours of t.c are not read here)
-      my_mask = block_mask16(gx, gy, q1.x, q1.y, q1.z, -__log2f(q0.w)) & live16;
-      my_opac = q0.w;
-    }
-    const bool clampy = __ballot(my_opac > CLAMP_FREE_OPACITY) != 0ull;
-    reinterpret_cast<uint4*>(lists4)[lane] = make_uint4(0x40404040u, 0x40404040u, 0x40404040u, 0x40404040u);
-    __syncthreads();
-    int cnt[16];
-#pragma unroll
-    for (int b = 0; b < 16; b++) {
-      const bool in = (my_mask >> b) & 1u;
-      const unsigned long long bal = __ballot(in);
-      cnt[b] = __popcll(bal);
-      if (in) lists[b * 64 + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = (unsigned char)lane;
-    }
-    __syncthreads();
-    auto walk = [&](auto mayclamp) {
-      constexpr bool MAYCLAMP = decltype(mayclamp)::value;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int b0 = 8 * (k >> 1) + 2 * (k & 1);
-        const int n = max(max(cnt[b0], cnt[b0 + 1]), max(cnt[b0 + 4], cnt[b0 + 5]));
-        const BLK_T* mylist = reinterpret_cast<const BLK_T*>(lists4) + myblock[k] * (64 / BLK_U);
-        for (int i4 = 0; BLK_U * i4 < n; i4++) {
-          const unsigned idx4 = mylist[i4];
-#pragma unroll
-          for (int e = 0; e < BLK_U; e++) {
-            const int j = (idx4 >> (8 * e)) & 0xffu;               // 64 = null record: s = 3e38, alpha = 0
-            const float4 qa = recs[j * 3], qb = recs[j * 3 + 1];
-            depth_stats_step<MAYCLAMP>(eval_s(qa, qb, pc, k), qb.z, j, batch_stop_code(j), Dhat[k],
-                                       T[k], smax[k], V[k], med[k]);
-          }
-        }
-      }
-    };
-    if (clampy) walk(std::true_type{}); else walk(std::false_type{});
-    // batch-relative codes -> final ones (4 selects per batch, not per entry)
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      smax[k] = finish_batch_stop(smax[k], base - start);
-      med[k] = med[k] >= 0 ? ~(base - start + med[k]) : med[k];
-    }
-  }
+  walk_blocks<false>(cam, splats, sorted_gid, tx, ty, start, end, pc, smax, recs,   // (the colours are neither staged nor read)
+                     [&](auto mayclamp, int k, float s, const float4& qb, const float4&, int j, int, float stopv) {
+                       depth_stats_step<decltype(mayclamp)::value>(s, qb.z, j, stopv, Dhat[k], T[k], smax[k], V[k], med[k]);
+                     },
+                     // the median's batch-relative code -> final one (one select per batch, not per entry)
+                     [&](int k, int rel) { med[k] = med[k] >= 0 ? ~(rel + med[k]) : med[k]; });
 #pragma unroll
   for (int k = 0; k < 4; k++)
     if (inb[k]) depth_stats_store(o, pix[k], V[k], fT[k], T[k], med[k], start, splats, sorted_gid);
@@ -2537,6 +2481,18 @@ extern "C" int tgs_set_k7_quad(int factor, int min_walk) {
   return g_k7_quad.get() | (g_k7_quad_min.get() << 8);
 }
 
+// The forward's split of tiles with long lists into quadrant blocks (raster_fwd_quadrant), also the launch shape of the
+// depth-statistics pass: grid + 3 * heads blocks -- three extra blocks for each of the schedule's first `heads` entries (the
+// longest lists of every XCD), which return at once unless their tile is split.  Off without a tile_order.
+static SplitRule make_split_rule(const TgsRasterOpts* opts, const int32_t* tile_order, int grid) {
+  SplitRule sr;
+  sr.factor = tile_order ? opt_or(opts, &TgsRasterOpts::k6_split, g_k6_split) : 0;
+  sr.n_slots = grid;
+  sr.heads = sr.factor > 0 ? min(grid, opt_or(opts, &TgsRasterOpts::k6_split_heads, g_k6_heads)) : 0;
+  sr.floor = max(64, opt_or(opts, &TgsRasterOpts::k6_split_floor, g_k6_floor));
+  return sr;
+}
+
 extern "C" int tgs_rasterize_fwd(const TgsCamera* cam, const float* splats,
                                  const int32_t* sorted_gid, int32_t* tile_start, int64_t tile_start_len,
                                  const int32_t* tile_order, float* out_rgb, float* out_depth,
@@ -2557,13 +2513,7 @@ extern "C" int tgs_rasterize_fwd(const TgsCamera* cam, const float* splats,
   // default: the 4x4-block form (-14.5 % at cfg3, bit-identical images); TGS_K6_BLOCKS=0 selects the quadrant
   // form, which also serves the slot_ok bitmaps.  TgsRasterOpts.k6_blocks / tgs_set_raster_variant switch it (tests, A/B).
   if (opt_or(opts, &TgsRasterOpts::k6_blocks, g_k6_blocks) && !slot_ok) {   // 4x4-block form (bit-identical images)
-    // tiles with long lists are split into quadrant blocks (raster_fwd_quadrant): three extra blocks for each of the
-    // schedule's first 512 entries (the longest lists of every XCD), which return at once unless their tile is split
-    SplitRule sr;
-    sr.factor = tile_order ? opt_or(opts, &TgsRasterOpts::k6_split, g_k6_split) : 0;
-    sr.n_slots = grid;
-    sr.heads = sr.factor > 0 ? min(grid, opt_or(opts, &TgsRasterOpts::k6_split_heads, g_k6_heads)) : 0;
-    sr.floor = max(64, opt_or(opts, &TgsRasterOpts::k6_split_floor, g_k6_floor));
+    const SplitRule sr = make_split_rule(opts, tile_order, grid);
     const int blocks = grid + 3 * sr.heads;
     if (final_idx)
       hipLaunchKernelGGL(k_raster_fwd_blocks<true>, dim3(blocks), dim3(64), 0, (hipStream_t)stream, k, T, splats,
@@ -2594,12 +2544,7 @@ extern "C" int tgs_rasterize_depth_stats(const TgsCamera* cam, const float* spla
   TGS_CHECK_ARG(tile_start_len >= (int64_t)T + 1 + TGS_TILE_START_SCRATCH,
                 "tile_start buffer shorter than tgs_tile_start_len(W, H) (the buffer of the forward these lists were composited with)");
   const int grid = TGS_XCDS * tgs_xcd_slots(T);
-  // K6's launch shape: long tiles in four quadrant blocks, by the rule (and the per-call fields) of the forward
-  SplitRule sr;
-  sr.factor = tile_order ? opt_or(opts, &TgsRasterOpts::k6_split, g_k6_split) : 0;
-  sr.n_slots = grid;
-  sr.heads = sr.factor > 0 ? min(grid, opt_or(opts, &TgsRasterOpts::k6_split_heads, g_k6_heads)) : 0;
-  sr.floor = max(64, opt_or(opts, &TgsRasterOpts::k6_split_floor, g_k6_floor));
+  const SplitRule sr = make_split_rule(opts, tile_order, grid);   // K6's launch shape, by the forward's rule and per-call fields
   DepthStatsOut o{depth_var, median_depth, median_gid};
   hipLaunchKernelGGL(k_raster_depth_stats, dim3(grid + 3 * sr.heads), dim3(64), 0, (hipStream_t)stream, k, T, splats,
                      sorted_gid, tile_start, out_depth, final_T, stop_pos, o, tile_order, sr);
