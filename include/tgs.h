@@ -552,7 +552,13 @@ int tgs_adam_step(int N, int sh_stride, float* params, const float* grads, float
  * out: block_partials[ceil(H/16)*ceil(W/16)] per-tile sums of the SSIM map (deterministic;
  *      mean SSIM = sum / (3*H*W)),
  *      v_img[H,W,3] = weight * d(sum of SSIM map)/d(img)   (NULL => forward only)
- * tmp: scratch[9*H*W] floats (needed when v_img != NULL). */
+ * tmp: scratch[9*H*W] floats (needed when v_img != NULL).
+ * Accuracy: the variances are formed as sigma = E[x^2] - mu^2 in fp32, and the map divides by sigma11 + sigma22 + C2
+ *     (C2 = 9e-4).  The error of the map and of v_img is therefore bounded in units of the fp32 conditioning of that
+ *     difference, per pixel u = 2^-24 ((E[x^2] + mu1^2 + E[y^2] + mu2^2 + 2|E[xy]| + 2|mu1 mu2| + C2) / (sigma11 + sigma22 + C2) + 8),
+ *     NOT by a fixed 1e-5: u is ~1e-6 on textured images and ~4e-4 on flat bright ones.  On a constant region every pixel
+ *     rounds alike, so the error of a sum of the map there is systematic and does not average out.  Bounds and measured
+ *     figures: tests/test_gpu_ssim_oracle.py (reference and unit: tests/ssim_ref.py). */
 int tgs_ssim_fwd_bwd(int W, int H, const float* img, const float* gt, float weight,
                      float* block_partials, float* v_img, float* scratch, void* stream);
 /* The same for the image rows [y0, y1) only (one band of a pipelined step, see tgs_rasterize_bwd_band):

@@ -450,6 +450,13 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
   for (int i = nwg + wg * NTH + tid; i < n_partials; i += nwg * NTH) block_partials[i] = 0.f;
 }
 
+// No forward row to produce (an empty band): nothing counts, but the caller still sums block_partials.  A kernel rather
+// than hipMemsetAsync, as in tgs_binning.h: an ordinary node when the step is captured into a hipGraph.
+__global__ void k_ssim_zero_partials(float* __restrict__ block_partials, int n_partials) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_partials) block_partials[i] = 0.f;
+}
+
 }  // namespace
 
 // the fused kernel counts a map pixel in the workgroup that owns its output row: the counted rows must be output rows
@@ -491,7 +498,15 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
   // forward rows: the gradient rows plus the 5-row halo the backward filter reads (adjoint maps)
   const int f0 = v_img ? max(0, y0 - HALO) : y0, f1 = v_img ? min(H, y1 + HALO) : y1;
   const int rows = f1 - f0;
-  if (rows <= 0) return TGS_OK;
+  if (rows <= 0) {
+    // the contract of include/tgs.h holds for an empty band too: workgroup sums (none), the rest zero
+    if (n_partials > 0) {
+      hipLaunchKernelGGL(k_ssim_zero_partials, dim3((n_partials + 255) / 256), dim3(256), 0, (hipStream_t)stream, block_partials,
+                         n_partials);
+      TGS_CHECK_LAUNCH();
+    }
+    return TGS_OK;
+  }
   const int sx = (W + SW - 1) / SW;
   int nblk = 4;
   while (nblk > 2 && (long long)sx * ((rows + seg_rows(nblk) - 1) / seg_rows(nblk)) < 3 * 256) nblk--;
