@@ -612,6 +612,41 @@ int tgs_depth_corr_local_fwd_bwd(int W, int H, const float* out_depth, const flo
                                  float* stats /*[16]*/, float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/,
                                  void* stream);
 
+/* Surface normals from the rendered depth, and the normal-prior loss (an ADDITION within TGS_VERSION 320: no struct and no
+ *     earlier signature changes; csrc/depthnormal.hip).
+ * in:  out_depth, final_T [H,W]: tgs_rasterize_fwd's outputs (out_depth is not divided by alpha); prior [H,W,3]: normals in
+ *      OpenCV camera axes, any length, length 0 = no supervision there (NULL = none anywhere); conf [H,W] or NULL: weights
+ *      >= 0 (NULL = 1 everywhere); cam: fx, fy, cx, cy, pix_center, W, H are read.
+ * Per pixel:  a = 1.0f - final_T in fp32; the pixel is VALID iff a >= alpha_min, compared in fp32 on the stored bits as in
+ *     tgs_depth_corr_fwd_bwd; alpha = max(a, 1e-10), x = out_depth / alpha; ray r(px, py) = ((px + pix_center - cx) / fx,
+ *     (py + pix_center - cy) / fy, 1); point P = x r.
+ * Centre i is FORMED iff it is an interior pixel (0 < px < W - 1, 0 < py < H - 1), it and its four neighbours l, r, u, d
+ *     are valid, max(|x_r - x_l|, |x_d - x_u|) <= max_jump * x_i in fp32 (the depth-discontinuity gate; max_jump <= 0
+ *     switches it off), and, with t_x = P_r - P_l, t_y = P_d - P_u, m = t_y x t_x, |m| > 0 and finite (decided on |m|^2 in
+ *     fp32, which must be a normal number: lengths from 1.1e-19 to 1.8e19).  n = m / |m|: a fronto-parallel plane gives
+ *     (0, 0, -1), the normal faces the camera.
+ * Centre i is SUPERVISED iff it is formed, |prior_i| > 0 and finite (on |prior_i|^2 in fp32, likewise) and c_i > 0.  p^ = prior / |prior|,
+ *     C = sum of c_i over the supervised centres,   L = weight * sum c_i (1 - n_i . p^_i) / C.
+ * Gradient (validity, the gates and C are constants of it): on a supervised centre k
+ *         g_n = -(weight c_k / C) p^_k,  g_m = (g_n - (g_n . n) n) / |m|,  g_tx = g_m x t_y,  g_ty = t_x x g_m    (0 elsewhere)
+ *     and for a pixel j   G_j = r_j . (g_tx(left neighbour of j) - g_tx(right) + g_ty(upper) - g_ty(lower)).
+ * out: stats[8] = {formed centres, supervised centres, C, sum c (1 - cos) / C, weight * [3], 0, 0, 0};
+ *      normals[H,W,3] (may be NULL) = n on formed centres and exactly 0 elsewhere;
+ *      v_depth[H,W] = G / alpha and v_alpha[H,W] = -G x / alpha (the gradient with respect to 1 - final_T): the upstream images
+ *      tgs_rasterize_bwd takes.  Every pixel is written.  Either may be NULL; both NULL = forward only (two launches
+ *      instead of three).  accumulate = 1: out = old + value, value = the bits the call with accumulate = 0 writes -- the
+ *      term stacks on the images tgs_depth_corr_fwd_bwd wrote without an add of its own; the caller orders the two calls
+ *      on one stream.
+ * tmp: tile_sums[tgs_num_tiles * 4] floats.  stats and tile_sums are 16-byte aligned; the images need no alignment.
+ * No supervised centre: loss 0, all gradients 0, nothing NaN.  No float atomics: the same inputs give the same bits.
+ * Accuracy: |n - n_ref| and G are held to 16 units of kappa_i 2^-24 resp. S_j 2^-24 (the condition numbers of the
+ * differences t_x, t_y; tests/depth_normal_ref.py, tests/test_gpu_depth_normal.py). */
+int tgs_depth_normal_fwd_bwd(const TgsCamera* cam, const float* out_depth, const float* final_T,
+                             const float* prior /*may be NULL*/, const float* conf /*may be NULL*/, float alpha_min,
+                             float max_jump, float weight, float* tile_sums, float* stats /*[8]*/,
+                             float* normals /*may be NULL*/, float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/,
+                             int accumulate, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

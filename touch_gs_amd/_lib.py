@@ -104,6 +104,8 @@ SIGNATURES = {
     "tgs_depth_corr_fwd_bwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "tgs_depth_corr_local_fwd_bwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, _I, _I, _I, _I, C.c_float,
                                               _P, _P, _P, _P, _P, _P]),
+    "tgs_depth_normal_fwd_bwd": (C.c_int, [C.POINTER(TgsCamera), _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P,
+                                          _P, _I, _P]),
     "tgs_peer_alloc": (C.c_int, [C.c_size_t, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "tgs_peer_open": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]),
     "tgs_peer_close": (C.c_int, [_P]),

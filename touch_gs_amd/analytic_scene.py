@@ -127,10 +127,12 @@ class AnalyticScene:
 
     # ---- cameras ---------------------------------------------------------------------------------------------
     def render(self, c2w_opengl: np.ndarray, intr: Sequence[float], W: int, H: int, ssaa: int = 2,
-               want_rgb: bool = True) -> Dict[str, np.ndarray]:
+               want_rgb: bool = True, want_normal: bool = False) -> Dict[str, np.ndarray]:
         """-> rgb [H,W,3] float32 (box-filtered ssaa x ssaa samples), depth [H,W] float64 (camera z of the ray
         through the pixel centre x + 0.5, y + 0.5 -- the convention of plumbing.get_point_cloud_from_depth_and_color
-        up to its half-pixel), object [H,W] bool."""
+        up to its half-pixel), object [H,W] bool.  ``want_normal``: also normal [H,W,3] float64, the exact unit surface
+        normal at the pixel centre's hit in the camera's OpenCV axes, facing the camera (z < 0 head-on), 0 where the ray
+        hits nothing."""
         fx, fy, cx, cy = intr
         c2w = torch.as_tensor(np.asarray(c2w_opengl, dtype=np.float64), dtype=self.dtype, device=self.device)
         Rcv = c2w[:3, :3] @ torch.diag(torch.tensor([1.0, -1.0, -1.0], dtype=self.dtype, device=self.device))
@@ -148,6 +150,11 @@ class AnalyticScene:
         depth = torch.where(torch.isfinite(t), t, torch.zeros_like(t)).reshape(H, W)      # d_cam z = 1 => z = t
         E = self.c.shape[0]
         out = {"depth": depth.cpu().numpy(), "object": ((prim >= 0) & (prim < E)).reshape(H, W).cpu().numpy()}
+        if want_normal:
+            nc = n @ Rcv                                                      # world -> camera (Rcv: camera -> world)
+            nc = torch.where(((n * dw).sum(-1) > 0)[:, None], -nc, nc)        # towards the camera
+            nc = torch.where((torch.isfinite(t) & (prim >= 0))[:, None], nc, torch.zeros_like(nc))
+            out["normal"] = nc.reshape(H, W, 3).cpu().numpy()
         if want_rgb:
             acc = torch.zeros(H * W, 3, dtype=self.dtype, device=self.device)
             for j in range(ssaa):

@@ -42,6 +42,12 @@ Monocular depth: ``mono_depth_dir`` (e.g. ``zoe_depth``, the pipeline's raw ZoeD
 ``<root>/<dir>/<image stem>.png`` (uint16) or ``.npy`` exists a ``View.mono_depth``, resized to the image like the
 sensor's depth.  No unit conversion and no dataparser scale: the term that reads it (ModelConfig.mono_depth_mult) is
 invariant to the map's scale and shift.
+
+Normal priors: ``normal_dir`` gives every view whose ``<root>/<dir>/<image stem>.npy`` (float [H,W,3]) or ``.png`` (RGB,
+n = 2 v / max - 1, a black pixel = no prior) exists a ``View.normal_prior`` in the view's OpenCV camera axes, and
+``<stem>_conf.npy`` [H,W], if present, its ``View.normal_conf``; resized by nearest neighbour (a blend of two normals is not
+a normal).  ``normal_frame="opengl"`` (the axes most monocular normal networks and renderers write: y up, z towards the
+viewer) flips y and z on load.  Any length: the term that reads them (ModelConfig.normal_prior_mult) normalises.
 """
 from __future__ import annotations
 
@@ -63,6 +69,46 @@ def _read_rgb(path: str) -> np.ndarray:
 
 
 UNCERTAINTY_SCALINGS = ("linear", "variance", "none")
+NORMAL_FRAMES = ("opencv", "opengl")
+
+
+def _resize_nearest(a: np.ndarray, H: int, W: int) -> np.ndarray:
+    """Nearest-neighbour resize of a [h,w,...] array (pixel centres, as torch's ``interpolate(mode="nearest")`` picks them)."""
+    h, w = a.shape[:2]
+    iy = np.minimum((np.arange(H) * (h / H)).astype(np.int64), h - 1)
+    ix = np.minimum((np.arange(W) * (w / W)).astype(np.int64), w - 1)
+    return a[iy][:, ix]
+
+
+def read_normal_map(base: str, H: int, W: int, frame: str = "opencv"):
+    """``base``.npy / .png (+ ``base``_conf.npy) -> (normals float32 [H,W,3] in OpenCV camera axes, conf float32 [H,W] or None),
+    or (None, None) if neither file exists.  See the module docstring."""
+    if os.path.exists(base + ".npy"):
+        n = np.load(base + ".npy").astype(np.float32)
+    elif os.path.exists(base + ".png"):
+        from PIL import Image
+        img = Image.open(base + ".png")
+        v = np.asarray(img.convert("RGB") if img.mode != "RGB" else img)
+        top = float(np.iinfo(v.dtype).max) if np.issubdtype(v.dtype, np.integer) else 1.0
+        n = (2.0 * v.astype(np.float32) / top - 1.0).astype(np.float32)
+        n[(v == 0).all(-1)] = 0.0
+    else:
+        return None, None
+    if n.ndim != 3 or n.shape[2] != 3:
+        raise ValueError(f"{base}: expected a [H,W,3] normal map, got shape {n.shape}")
+    if n.shape[:2] != (H, W):
+        n = _resize_nearest(n, H, W)
+    if frame == "opengl":
+        n = n * np.array([1.0, -1.0, -1.0], np.float32)
+    conf = None
+    if os.path.exists(base + "_conf.npy"):
+        conf = np.load(base + "_conf.npy").astype(np.float32)
+        if conf.ndim != 2:
+            raise ValueError(f"{base}_conf.npy: expected a [H,W] map, got shape {conf.shape}")
+        if conf.shape != (H, W):
+            conf = _resize_nearest(conf, H, W)
+        conf = np.ascontiguousarray(conf)
+    return np.ascontiguousarray(n, dtype=np.float32), conf
 
 
 def uncertainty_factor(scaling: str, depth_unit_scale_factor: float, dataparser_scale: float) -> float:
@@ -76,9 +122,12 @@ class Scene:
                  depth_unit_scale_factor: float = 1e-3, real_world: Optional[bool] = None,
                  gt_depth_dir: str = "realsense_depths", object_mask_dir: str = "touch_depth",
                  uncertainty_scaling: str = "linear", uncertainty_floor: float = 0.0,
-                 mono_depth_dir: Optional[str] = None):
+                 mono_depth_dir: Optional[str] = None, normal_dir: Optional[str] = None, normal_frame: str = "opencv"):
         self.root = root
         self.mono_depth_dir = mono_depth_dir
+        if normal_frame not in NORMAL_FRAMES:
+            raise ValueError(f"normal_frame must be one of {NORMAL_FRAMES}")
+        self.normal_dir, self.normal_frame = normal_dir, normal_frame
         if uncertainty_scaling not in UNCERTAINTY_SCALINGS:
             raise ValueError(f"uncertainty_scaling must be one of {UNCERTAINTY_SCALINGS}")
         self.uncertainty_scaling = uncertainty_scaling
@@ -130,6 +179,12 @@ class Scene:
                             view.object_mask = torch.from_numpy(m).to(device)
             if mono_depth_dir:
                 view.mono_depth = self._read_mono(os.path.splitext(os.path.basename(fr["file_path"]))[0], H, W, device)
+            if normal_dir:
+                stem = os.path.splitext(os.path.basename(fr["file_path"]))[0]
+                n, conf = read_normal_map(os.path.join(root, normal_dir, stem), H, W, normal_frame)
+                if n is not None:
+                    view.normal_prior = torch.from_numpy(n).to(device)
+                    view.normal_conf = None if conf is None else torch.from_numpy(conf).to(device)
             self.views.append(view)
         names = [fr["file_path"] for fr in frames]
         self.names = names
@@ -157,6 +212,8 @@ class Scene:
         return dict(dataparser_scale=self.scale, depth_unit_scale_factor=self.depth_unit_scale_factor,
                     uncertainty_scaling=self.uncertainty_scaling, uncertainty_floor=self.uncertainty_floor,
                     mono_depth_dir=self.mono_depth_dir, mono_depth_views=sum(v.mono_depth is not None for v in self.views),
+                    normal_dir=self.normal_dir, normal_frame=self.normal_frame,
+                    normal_views=sum(v.normal_prior is not None for v in self.views),
                     uncertainty_factor=uncertainty_factor(self.uncertainty_scaling, self.depth_unit_scale_factor,
                                                           self.scale))
 

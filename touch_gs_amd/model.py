@@ -62,6 +62,13 @@ class ModelConfig:
     mono_depth_patch_tiles: int = 8
     mono_depth_patch_min_fill: float = 0.25
     mono_depth_patch_min_var: float = 1e-3
+    # normal-prior term  normal_prior_mult * (conf-weighted mean of 1 - cos(angle between the normal of the rendered depth
+    # and View.normal_prior))  (ops.depth_normal_fwd_bwd).  0 = off: no launch, nothing changes.  A normal is
+    # formed where a pixel and its four neighbours have alpha >= normal_alpha_min and the depth steps by at most
+    # normal_max_jump of the centre's depth (<= 0: no such gate)
+    normal_prior_mult: float = 0.0
+    normal_alpha_min: float = 0.5
+    normal_max_jump: float = 0.1
     sh_degree_interval: int = 1000
     # Splatfacto's coarse-to-fine schedule (num_downscales 2, resolution_schedule 250): training
     # starts on images downscaled by 2^num_downscales and doubles the resolution every resolution_schedule steps.
@@ -143,6 +150,11 @@ class View:
     # raw monocular depth (e.g. ZoeDepth), 0 = no value, any positive units: supervises through the correlation term
     # (ModelConfig.mono_depth_mult), which is invariant to its scale and shift -- no alignment to a depth sensor needed
     mono_depth: Optional[torch.Tensor] = None   # [H,W]
+    # surface-normal prior in this camera's OpenCV axes (x right, y down, z forward: a surface seen head-on is (0, 0, -1)),
+    # any length, length 0 = no prior at that pixel, and optional weights >= 0: supervise the normals of the rendered depth
+    # (ModelConfig.normal_prior_mult)
+    normal_prior: Optional[torch.Tensor] = None  # [H,W,3]
+    normal_conf: Optional[torch.Tensor] = None   # [H,W]
 
     def valid_count(self) -> int:
         if self.n_valid_depth is None:
@@ -152,8 +164,8 @@ class View:
     def downscaled(self, d: int) -> "View":
         """This view at 1/d of its resolution (cached): the colour image resized bilinearly to (H // d, W // d) --
         what Splatfacto's ``_downscale_if_required`` does (torchvision resize of a tensor, no antialiasing) --
-        depth, uncertainty and mono_depth by nearest neighbour, so that 0 stays "unsupervised" and no depth is invented across
-        an object boundary; camera as ``Camera.downscaled``."""
+        depth, uncertainty, mono_depth, normal_prior and normal_conf by nearest neighbour, so that 0 stays "unsupervised" and
+        no depth (or normal) is invented across an object boundary; camera as ``Camera.downscaled``."""
         if d <= 1:
             return self
         cache = self.__dict__.setdefault("_downscaled", {})
@@ -163,8 +175,11 @@ class View:
             rgb = F.interpolate(self.rgb.permute(2, 0, 1)[None], size=(H, W), mode="bilinear", align_corners=False,
                                 antialias=False)[0].permute(1, 2, 0).contiguous()
             near = lambda t: None if t is None else F.interpolate(t[None, None].float(), size=(H, W), mode="nearest")[0, 0].to(t.dtype).contiguous()
+            near3 = lambda t: None if t is None else F.interpolate(t.permute(2, 0, 1)[None].float(), size=(H, W),
+                                                                   mode="nearest")[0].permute(1, 2, 0).to(t.dtype).contiguous()
             cache[d] = View(cam=self.cam.downscaled(d), rgb=rgb, depth=near(self.depth), uncertainty=near(self.uncertainty),
-                            gt_depth=near(self.gt_depth), object_mask=near(self.object_mask), mono_depth=near(self.mono_depth))
+                            gt_depth=near(self.gt_depth), object_mask=near(self.object_mask), mono_depth=near(self.mono_depth),
+                            normal_prior=near3(self.normal_prior), normal_conf=near(self.normal_conf))
         return cache[d]
 
 
@@ -219,8 +234,12 @@ class DepthGaussianSplattingModel:
             return min(c.sh_degree, max_deg)
         return min((self.step if step is None else step) // c.sh_degree_interval, c.sh_degree, max_deg)
 
-    def get_outputs(self, cam: Camera, sh_degree: Optional[int] = None, depth_stats: bool = False) -> Dict[str, torch.Tensor]:
+    def get_outputs(self, cam: Camera, sh_degree: Optional[int] = None, depth_stats: bool = False,
+                    normals: bool = False) -> Dict[str, torch.Tensor]:
         """Camera -> {rgb, depth, accumulation} (differentiable; autograd path).
+
+        ``normals=True`` adds ``normal`` [H,W,3]: the unit normals of the rendered depth in the camera's OpenCV axes
+        (ops.depth_normals with the config's normal_alpha_min / normal_max_jump; exactly 0 where none is formed), detached.
 
         ``depth_stats=True`` adds ``median_depth`` [H,W,1] (depth of the Gaussian behind which the transmittance first is
         <= 1/2; 0 where alpha < 1/2), ``depth_var`` / ``depth_std`` [H,W,1] (spread of depth along the ray around the
@@ -248,6 +267,9 @@ class DepthGaussianSplattingModel:
             var, med, gid = stats
             out.update(median_depth=med[..., None], depth_var=var[..., None], depth_std=torch.sqrt(var)[..., None],
                        median_gid=gid)
+        if normals:
+            out["normal"] = ops.depth_normals(cam, depth_acc, 1.0 - alpha.detach(), self.config.normal_alpha_min,
+                                              self.config.normal_max_jump)
         return out
 
     def depth_loss(self, depth_acc, alpha, view: View) -> torch.Tensor:
@@ -283,7 +305,14 @@ class DepthGaussianSplattingModel:
         elif self.mono_depth_active(view):
             rho = ops.depth_correlation(outputs["depth_acc"], outputs["alpha"], view.mono_depth, c.mono_depth_alpha_min)
             loss["mono_depth_loss"] = c.mono_depth_mult * (1 - rho)
+        if self.normal_prior_active(view):
+            loss["normal_loss"] = c.normal_prior_mult * ops.depth_normal_loss(
+                view.cam, outputs["depth_acc"], outputs["alpha"], view.normal_prior, view.normal_conf, c.normal_alpha_min,
+                c.normal_max_jump)
         return loss
+
+    def normal_prior_active(self, view: View) -> bool:
+        return self.config.normal_prior_mult > 0 and view.normal_prior is not None
 
     def mono_depth_active(self, view: View) -> bool:
         return self.config.mono_depth_mult > 0 and view.mono_depth is not None
@@ -344,6 +373,17 @@ class DepthGaussianSplattingModel:
                     metrics["gt_object_depth_mse_median"] = mse_of(view.gt_depth, valid & view.object_mask)
             images["median_depth"] = outputs["median_depth"]
             images["depth_std"] = outputs["depth_std"]
+        if "normal" in outputs:   # get_outputs(normals=True)
+            images["normal"] = 0.5 * (outputs["normal"] + 1.0)
+            if view.normal_prior is not None:
+                # conf-weighted mean angle to the prior over the supervised centres (formed, prior of non-zero length, c > 0)
+                n, p = outputs["normal"], view.normal_prior
+                pl = p.norm(dim=-1)
+                w = torch.ones_like(pl) if view.normal_conf is None else view.normal_conf
+                sup = (n.abs().sum(-1) > 0) & (pl > 0) & torch.isfinite(pl) & (w > 0)
+                cos = ((n * p).sum(-1) / pl.clamp(min=1e-30)).clamp(-1.0, 1.0)
+                ang = torch.rad2deg(torch.acos(cos))
+                metrics["normal_angle_deg"] = float((w * ang)[sup].sum() / w[sup].sum()) if sup.any() else 0.0
         return metrics, images
 
     # -- fused train step ---------------------------------------------------------------------
@@ -386,8 +426,13 @@ class DepthGaussianSplattingModel:
         elif self.mono_depth_active(view):   # image-space term beside K7, which adds its fused terms on top of the two images
             mono_stats, v_depth, v_alpha = ops.depth_corr_fwd_bwd(depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min,
                                                                   weight=c.mono_depth_mult)
+        normal_stats = None
+        if self.normal_prior_active(view):   # after the Pearson op, on the same stream: the term adds to its two images
+            normal_stats, _, v_depth, v_alpha = ops.depth_normal_fwd_bwd(
+                cam, depth_acc, fT, view.normal_prior, view.normal_conf, c.normal_alpha_min, c.normal_max_jump,
+                weight=c.normal_prior_mult, accumulate_into=None if mono_stats is None else (v_depth, v_alpha))
         if (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles and mono_stats is None
-                and not torch.cuda.is_current_stream_capturing()):
+                and normal_stats is None and not torch.cuda.is_current_stream_capturing()):
             if getattr(self, "_side_stream", None) is None:
                 self._side_stream = torch.cuda.Stream(device=rgb.device)
             partials, tile_loss, ssim_sum = ops.rasterize_bwd_ssim_pipelined(
@@ -427,6 +472,8 @@ class DepthGaussianSplattingModel:
             self.last["mono_stats"] = mono_stats
         if patch_off is not None:
             self.last["mono_patch_offset"] = patch_off
+        if normal_stats is not None:
+            self.last["normal_stats"] = normal_stats
         return tile_loss, ssim_sum
 
     def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None) -> Dict[str, torch.Tensor]:
@@ -446,6 +493,8 @@ class DepthGaussianSplattingModel:
                 out["mono_depth_loss"] = mono_stats[7]    # weight * (1 - rho), weight = mono_depth_mult
             if mono_stats.numel() == 16:                  # the local term was active in that step
                 out["mono_depth_local_loss"] = mono_stats[11]     # mono_depth_local_mult * (1 - rho_bar)
+        if self.last.get("tile_loss") is tile_loss and self.last.get("normal_stats") is not None:
+            out["normal_loss"] = self.last["normal_stats"][4]     # normal_prior_mult * (mean of 1 - cos)
         return out
 
     def spatial_sort(self) -> torch.Tensor:

@@ -1041,3 +1041,81 @@ def depth_correlation_local(depth_acc, alpha, mono, alpha_min: float = 0.5, patc
     active patches (:func:`depth_corr_local_fwd_bwd`), device scalars differentiable in ``depth_acc`` and ``alpha`` with the
     gates held constant.  No host sync."""
     return _DepthCorrelationLocal.apply(depth_acc, alpha, mono, alpha_min, patch_tiles, tuple(offset), min_fill, min_var_ratio)
+
+
+# ------------------------------------------------------------------------------------------------
+# image-space kernels: surface normals of the rendered depth and the normal-prior loss (csrc/depthnormal.hip, DESIGN 5.1i)
+# ------------------------------------------------------------------------------------------------
+def depth_normal_fwd_bwd(cam: Camera, depth_acc, final_T, prior, conf=None, alpha_min: float = 0.5, max_jump: float = 0.1,
+                         weight: float = 1.0, want_grad: bool = True, want_normals: bool = False, accumulate_into=None):
+    """-> (stats [8], normals [H,W,3] or None, v_depth [H,W] or None, v_alpha [H,W] or None).  (tgs_depth_normal_fwd_bwd)
+
+    Normals n of the surface through the back-projected expected depths ``depth_acc / max(1 - final_T, 1e-10)`` (central
+    differences over a pixel's four neighbours, OpenCV camera axes, facing the camera; formed where the five pixels have
+    ``1 - final_T >= alpha_min`` and the depth steps by at most ``max_jump`` of the centre's depth, ``max_jump <= 0`` = no
+    gate), and the loss ``weight * sum c (1 - n . prior / |prior|) / sum c`` over the formed centres with a prior of non-zero
+    length and ``conf`` c > 0 (``conf=None``: 1 everywhere; ``prior=None``: no supervision).
+    stats = {formed centres, supervised centres, sum c, mean 1 - cos, weight * mean, 0, 0, 0}; ``v_depth`` / ``v_alpha`` =
+    gradient of the loss with respect to ``depth_acc`` / ``1 - final_T``: the upstream images :func:`rasterize_bwd` takes.
+    ``accumulate_into=(v_depth, v_alpha)``: the gradient is ADDED to these two images (those :func:`depth_corr_fwd_bwd`
+    wrote, on the same stream) and they are returned.  No supervised centre: loss 0 and zero gradients.  No host sync.
+    """
+    lib = _lib.load()
+    depth_acc, final_T = _f32c(depth_acc.detach()), _f32c(final_T.detach())
+    H, W = cam.H, cam.W
+    if depth_acc.shape != (H, W) or final_T.shape != (H, W):
+        raise ValueError(f"depth_acc and final_T must be [H,W] = [{H},{W}] of the camera, got {tuple(depth_acc.shape)}, "
+                         f"{tuple(final_T.shape)}")
+    prior, conf = _f32c(prior), _f32c(conf)
+    if prior is not None and prior.shape != (H, W, 3):
+        raise ValueError(f"prior must be [H,W,3], got {tuple(prior.shape)}")
+    if conf is not None and (prior is None or conf.shape != (H, W)):
+        raise ValueError("conf must be [H,W] and needs a prior")
+    dev = depth_acc.device
+    tiles = torch.empty(((H + 15) // 16) * ((W + 15) // 16), 4, dtype=torch.float32, device=dev)
+    stats = torch.empty(8, dtype=torch.float32, device=dev)
+    normals = torch.empty(H, W, 3, dtype=torch.float32, device=dev) if want_normals else None
+    v_depth = v_alpha = None
+    if accumulate_into is not None:
+        v_depth, v_alpha = accumulate_into
+        for t in (v_depth, v_alpha):
+            if t.dtype != torch.float32 or t.shape != (H, W) or not t.is_contiguous() or t.device != dev:
+                raise ValueError("accumulate_into must be two contiguous float32 [H,W] images on the images' device")
+    elif want_grad:
+        v_depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        v_alpha = torch.empty(H, W, dtype=torch.float32, device=dev)
+    cs = cam.c_struct()
+    check(lib.tgs_depth_normal_fwd_bwd(C.byref(cs), ptr(depth_acc), ptr(final_T), ptr(prior), ptr(conf), C.c_float(alpha_min),
+                                       C.c_float(max_jump), C.c_float(weight), ptr(tiles), ptr(stats), ptr(normals),
+                                       ptr(v_depth), ptr(v_alpha), 1 if accumulate_into is not None else 0, _stream()),
+          "tgs_depth_normal_fwd_bwd")
+    return stats, normals, v_depth, v_alpha
+
+
+def depth_normals(cam: Camera, depth_acc, final_T, alpha_min: float = 0.5, max_jump: float = 0.1):
+    """The normals image [H,W,3] of :func:`depth_normal_fwd_bwd` alone (forward only, no prior): unit normals in OpenCV camera
+    axes on the formed centres, exactly 0 elsewhere."""
+    return depth_normal_fwd_bwd(cam, depth_acc, final_T, None, None, alpha_min, max_jump, 0.0, want_grad=False,
+                                want_normals=True)[1]
+
+
+class _DepthNormalLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth_acc, alpha, prior, conf, cam, alpha_min, max_jump):
+        # 1 - (1 - T) restores the bits of 1 - T for every T in [0, 1]: the kernel sees the alpha the renderer returned
+        stats, _, v_depth, v_alpha = depth_normal_fwd_bwd(cam, depth_acc, 1.0 - alpha.detach(), prior, conf, alpha_min, max_jump,
+                                                          weight=1.0)
+        ctx.save_for_backward(v_depth, v_alpha)
+        return stats[3].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        v_depth, v_alpha = ctx.saved_tensors
+        return g * v_depth, g * v_alpha, None, None, None, None, None
+
+
+def depth_normal_loss(cam: Camera, depth_acc, alpha, prior, conf=None, alpha_min: float = 0.5, max_jump: float = 0.1):
+    """The conf-weighted mean of 1 - cos(angle between the depth-derived normal and the prior) over the supervised centres
+    (:func:`depth_normal_fwd_bwd`), a device scalar differentiable in ``depth_acc`` and ``alpha`` with validity, the gates and
+    the weight sum held constant; ``depth_acc`` / ``alpha`` as :func:`render` returns them.  No host sync."""
+    return _DepthNormalLoss.apply(depth_acc, alpha, prior, conf, cam, alpha_min, max_jump)

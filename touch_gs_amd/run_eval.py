@@ -22,10 +22,13 @@ import os
 import torch
 
 
-def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False) -> dict:
+def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False,
+             normals: bool = False, normal_dir=None, normal_frame=None) -> dict:
     """Rebuild the model of one training run from its config.json + newest checkpoint and evaluate
     it on the run's eval split.  ``depth_stats``: the results gain median_depth_mse / gt_depth_mse_median /
-    gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views)."""
+    gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views).  ``normals``: the
+    results gain normal_angle_deg (against the run's own normal priors, or those of ``normal_dir`` / ``normal_frame`` if
+    given) and the render dump normal/."""
     from .dataset import Scene
     from .model import DepthGaussianSplattingModel, ModelConfig
     from .optim import GaussianParams
@@ -46,17 +49,19 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
         views = [make_view(N, W, H, cfg["sh_degree"], 1235, device, view=7, n_views=8)]
         names, scale = None, 1.0
     else:
-        scene = Scene(cfg["data"], cfg["train_split_fraction"], device)
+        scene = Scene(cfg["data"], cfg["train_split_fraction"], device,
+                      normal_dir=(normal_dir or cfg.get("normal_dir")) if normals else None,
+                      normal_frame=normal_frame or cfg.get("normal_frame") or "opencv")
         idx = list(scene.i_eval) or list(scene.i_train)[:1]
         views, names, scale = [scene.views[i] for i in idx], [scene.names[i] for i in idx], scene.scale
-    results = evaluate(model, views, depth_stats=depth_stats)
+    results = evaluate(model, views, depth_stats=depth_stats, normals=normals)
     results.setdefault("lpips", float("nan"))   # get_results.py:38 indexes it unconditionally
     os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
     with open(out_json, "w") as f:
         json.dump({"experiment_name": os.path.basename(os.path.dirname(os.path.dirname(run_dir))),
                    "method_name": "depth-gaussian-splatting", "checkpoint": ckpts[-1], "results": results}, f, indent=2)
     if render_dir:
-        render_views(model, views, render_dir, names, depth_stats=depth_stats, dataparser_scale=scale)
+        render_views(model, views, render_dir, names, depth_stats=depth_stats, dataparser_scale=scale, normals=normals)
     return results
 
 
@@ -70,6 +75,9 @@ def main(argv=None):
     ap.add_argument("--depth-stats", "--depth_stats", dest="depth_stats", action="store_true",
                     help="also evaluate the median depth and dump median_depth/ + uncertainty/ (rendered depth variance, "
                          "uint16 like the input uncertainty maps)")
+    ap.add_argument("--normals", action="store_true",
+                    help="also render the normals of the depth: normal/ PNGs ((n + 1) / 2, OpenCV camera axes) and, for runs "
+                         "trained with --normal-dir, normal_angle_deg")
     a = ap.parse_args(argv)
     full_exp_dir = os.path.join(a.output_dir, a.exp_name)
     os.makedirs(full_exp_dir, exist_ok=True)
@@ -79,7 +87,8 @@ def main(argv=None):
         if not os.path.exists(os.path.join(run_dir, "config.json")):
             continue
         out_json = os.path.join(full_exp_dir, f"{a.exp_name}_{len(done) + 1}.json")
-        res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders", depth_stats=a.depth_stats)
+        res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders", depth_stats=a.depth_stats,
+                       normals=a.normals)
         print(out_json, json.dumps(res))
         done.append(out_json)
         if len(done) == a.past_n_trials:

@@ -78,13 +78,15 @@ def init_params(n: int, K: int, device, seed_points=None, extent: float = 1.0, s
 
 
 @torch.no_grad()
-def evaluate(model: DepthGaussianSplattingModel, views, depth_stats: bool = False) -> dict:
+def evaluate(model: DepthGaussianSplattingModel, views, depth_stats: bool = False, normals: bool = False) -> dict:
     """Mean of the eval metrics over ``views``.  ``depth_stats``: also median_depth_mse / gt_depth_mse_median /
-    gt_object_depth_mse_median (the median depth under the masks of the expected-depth keys, whose values do not change)."""
+    gt_object_depth_mse_median (the median depth under the masks of the expected-depth keys, whose values do not change).
+    ``normals``: also normal_angle_deg over the views that carry a normal prior."""
     acc = {}
+    kw = dict(normals=True) if normals else {}
     for v in views:
-        out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True) if depth_stats else
-               model.get_outputs(v.cam, sh_degree=model.active_sh_degree()))
+        out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True, **kw) if depth_stats else
+               model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), **kw))
         m, _ = model.get_image_metrics_and_images(out, v)
         for k, x in m.items():
             acc.setdefault(k, []).append(x)
@@ -102,12 +104,14 @@ def uncertainty_png(depth_var, dataparser_scale: float = 1.0):
 
 
 def render_views(model: DepthGaussianSplattingModel, views, out_dir: str, names=None, depth_stats: bool = False,
-                 dataparser_scale: float = 1.0) -> None:
+                 dataparser_scale: float = 1.0, normals: bool = False) -> None:
     """The build's counterpart of ``ns-render dataset`` (reference experiment_utils/run_eval.py:48):
     ``<out_dir>/rgb/<name>.png`` (8-bit) and ``<out_dir>/depth/<name>.png`` (uint16 millimetres, the
     convention of the dataset's own depth maps: utils/fuse_touch_vision.py:372-376).
     ``depth_stats``: also ``median_depth/<name>.png`` (like depth/) and ``uncertainty/<name>.png``, the rendered depth
-    variance in the format of the input uncertainty maps (``uncertainty_png``; ``dataparser_scale`` = Scene.scale)."""
+    variance in the format of the input uncertainty maps (``uncertainty_png``; ``dataparser_scale`` = Scene.scale).
+    ``normals``: also ``normal/<name>.png``, the normals of the rendered depth in the camera's OpenCV axes as 8-bit RGB
+    (n + 1) / 2, black where none is formed -- the encoding ``dataset.read_normal_map`` reads back."""
     from PIL import Image
     from .plumbing import write_png16
     os.makedirs(os.path.join(out_dir, "rgb"), exist_ok=True)
@@ -115,14 +119,21 @@ def render_views(model: DepthGaussianSplattingModel, views, out_dir: str, names=
     if depth_stats:
         os.makedirs(os.path.join(out_dir, "median_depth"), exist_ok=True)
         os.makedirs(os.path.join(out_dir, "uncertainty"), exist_ok=True)
+    kw = dict(normals=True) if normals else {}
+    if normals:
+        os.makedirs(os.path.join(out_dir, "normal"), exist_ok=True)
     for i, v in enumerate(views):
-        out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True) if depth_stats else
-               model.get_outputs(v.cam, sh_degree=model.active_sh_degree()))
+        out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True, **kw) if depth_stats else
+               model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), **kw))
         name = os.path.splitext(os.path.basename(names[i]))[0] if names else f"{i:05d}"
         rgb = (out["rgb"].clamp(0, 1) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
         Image.fromarray(rgb).save(os.path.join(out_dir, "rgb", name + ".png"))
         mm = (out["depth"].reshape(v.cam.H, v.cam.W) * 1000.0).clamp(0, 65535).round().to(torch.int32).cpu().numpy()
         write_png16(os.path.join(out_dir, "depth", name + ".png"), mm.astype("uint16"))
+        if normals:
+            n = out["normal"]
+            img = torch.where(n.abs().sum(-1, keepdim=True) > 0, (0.5 * (n + 1.0) * 255.0 + 0.5).clamp(1, 255), torch.zeros_like(n))
+            Image.fromarray(img.to(torch.uint8).cpu().numpy()).save(os.path.join(out_dir, "normal", name + ".png"))
         if depth_stats:
             mm = (out["median_depth"].reshape(v.cam.H, v.cam.W) * 1000.0).clamp(0, 65535).round().to(torch.int32).cpu().numpy()
             write_png16(os.path.join(out_dir, "median_depth", name + ".png"), mm.astype("uint16"))
@@ -166,6 +177,18 @@ def main(argv=None):
                     help="a patch counts with at least this share of its area valid")
     ap.add_argument("--mono-depth-patch-min-var", type=float, default=1e-3,
                     help="a patch counts with both variances at least this share of the image's")
+    ap.add_argument("--normal-dir", type=str, default=None,
+                    help="folder under --data with one normal prior per image (<image stem>.npy float [H,W,3], or .png RGB with "
+                         "n = 2 v / max - 1; optional <stem>_conf.npy weights): supervises the normals of the rendered depth")
+    ap.add_argument("--normal-frame", type=str, default="opencv", choices=("opencv", "opengl"),
+                    help="camera axes of the maps; opengl (y up, z towards the viewer) flips y and z on load")
+    ap.add_argument("--normal-mult", type=float, default=0.0,
+                    help="weight of the conf-weighted mean of 1 - cos(angle between rendered-depth normal and prior); 0 = off")
+    ap.add_argument("--normal-max-jump", type=float, default=0.1,
+                    help="no normal across a depth step larger than this share of the depth (<= 0: no such gate)")
+    ap.add_argument("--eval-normals", action="store_true",
+                    help="final evaluation also renders the normals of the depth: eval.json gains normal_angle_deg (views "
+                         "with a prior), --render-output gains normal/")
     ap.add_argument("--max-num-iterations", type=int, default=30000)
     ap.add_argument("--steps-per-save", type=int, default=2000)
     ap.add_argument("--steps-per-eval", type=int, default=500)
@@ -221,7 +244,10 @@ def main(argv=None):
     else:
         from .dataset import Scene
         scene = Scene(args.data, args.train_split_fraction, dev, uncertainty_scaling=args.uncertainty_scaling,
-                      uncertainty_floor=args.uncertainty_floor, mono_depth_dir=args.mono_depth_dir)
+                      uncertainty_floor=args.uncertainty_floor, mono_depth_dir=args.mono_depth_dir,
+                      normal_dir=args.normal_dir, normal_frame=args.normal_frame)
+        if args.normal_mult > 0 and not any(v.normal_prior is not None for v in scene.views):
+            raise SystemExit("--normal-mult > 0 needs --normal-dir with at least one map")
         if (args.mono_depth_mult > 0 or args.mono_depth_local_mult > 0) and not any(v.mono_depth is not None for v in scene.views):
             raise SystemExit("--mono-depth-mult > 0 needs --mono-depth-dir with at least one map")
         views, i_train, i_eval = scene.views, list(scene.i_train), list(scene.i_eval)
@@ -234,7 +260,8 @@ def main(argv=None):
                       resolution_schedule=args.resolution_schedule, mono_depth_mult=args.mono_depth_mult,
                       mono_depth_alpha_min=args.mono_depth_alpha_min, mono_depth_local_mult=args.mono_depth_local_mult,
                       mono_depth_patch_tiles=args.mono_depth_patch_tiles, mono_depth_patch_min_fill=args.mono_depth_patch_min_fill,
-                      mono_depth_patch_min_var=args.mono_depth_patch_min_var)
+                      mono_depth_patch_min_var=args.mono_depth_patch_min_var, normal_prior_mult=args.normal_mult,
+                      normal_max_jump=args.normal_max_jump)
     model = DepthGaussianSplattingModel(cfg, params)
     if cfg.spatial_sort:
         model.spatial_sort()
@@ -310,7 +337,7 @@ def main(argv=None):
         print(f"gaussians {model.params.N}  refinements {n_refines}  speculative replays "
               f"{getattr(model, 'speculative_replays', 0)}", flush=True)
     if dp.rank == 0:
-        results = evaluate(model, eval_views, depth_stats=args.eval_depth_stats)
+        results = evaluate(model, eval_views, depth_stats=args.eval_depth_stats, normals=args.eval_normals)
         # the reference's aggregator indexes results['lpips'] unconditionally
         # (experiment_utils/get_results.py:38); LPIPS needs pretrained network weights that cannot be
         # fetched here, so the key is present and NaN rather than absent
@@ -322,7 +349,8 @@ def main(argv=None):
         if args.render_output:
             render_views(model, eval_views, args.render_output,
                          None if args.synthetic is not None else [scene.names[i] for i in i_eval] if i_eval else None,
-                         depth_stats=args.eval_depth_stats, dataparser_scale=1.0 if args.synthetic is not None else scene.scale)
+                         depth_stats=args.eval_depth_stats, dataparser_scale=1.0 if args.synthetic is not None else scene.scale,
+                         normals=args.eval_normals)
     dp.barrier()
     if dp.peer is not None:
         dp.peer.close()
