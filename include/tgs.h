@@ -647,6 +647,45 @@ int tgs_depth_normal_fwd_bwd(const TgsCamera* cam, const float* out_depth, const
                              float* normals /*may be NULL*/, float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/,
                              int accumulate, void* stream);
 
+/* A Gaussian-process implicit surface (GPIS) ray-marched into one view: touch depth, posterior variance and surface normal
+ *     (an ADDITION within TGS_VERSION 320: a new struct and a new call, nothing earlier changes; csrc/gpis.hip).
+ *     The device form of touch_gs_amd.gpis.GPIS.render_depth, which stays the definition.
+ * ALL coordinates (X, P, view->t) are CENTRED on the centroid of P by the caller, in fp64, before they are rounded to fp32.
+ * in:  X [n,4] = {x, y, z, alpha}: the GP's points and weights (16-byte aligned); P, N [n_p,3]: the touched points and their
+ *      outward unit normals; Kinv [n,n] fp64 = (K + noise I)^-1, NULL = no variance wanted (var, if given, is all NaN and
+ *      max_var must be negative); l, sf2, prior: length scale, signal variance, the "far outside" prior mean.
+ * view: the camera -- R = its OpenCV axes in the world, row-major (row = world axis, column = camera axis: a world direction
+ *      is R d_cam), t = its centred position, fx, fy, cx, cy, W, H; pixel (u, v) looks along ((u + 0.5 - cx) / fx,
+ *      (v + 0.5 - cy) / fy, 1) --, the region of interest u0 <= u <= u1, v0 <= v <= v1 (inside the image) of which every
+ *      stride-th pixel from (u0, v0) is rendered, and the march: samples z_k = z_lo + k dz, k < n_steps (2 ... 512), of the
+ *      camera-space depth; max_var < 0 = no cut; var_floor.
+ * Per rendered ray:  m(q) = sum_j alpha_j k_j + prior (1 - max_j k_j / sf2),  k_j = sf2 exp(-|q - x_j|^2 / 2 l^2), in fp32, the
+ *      squared distance as a sum of squared differences.  The first k >= 1 with m(z_{k-1}) > 0 and m(z_k) <= 0 brackets the
+ *      crossing; 12 bisection rounds; z = the last bracket's midpoint.  The crossing counts iff the outward normal of the touched
+ *      point nearest to it (brute force, lowest index on ties) has N . ray / |ray| < -0.05, and, with max_var >= 0, iff
+ *      var <= max_var, where  var = max(sf2 - k^T Kinv k, 0)  (k in fp32, widened; fp64 accumulation in a fixed order).
+ * out: depth [H,W] = z, var [H,W] = max(var, var_floor) on the counted crossings, NaN on every other pixel of the image;
+ *      normal [H,W,3] (may be NULL) = grad m / |grad m| at the crossing, rotated into the camera's OpenCV axes (not flipped:
+ *      m grows outwards), exactly 0 elsewhere;  grad m = sum_j alpha_j k_j (x_j - q) / l^2 - prior k_J (x_J - q) / (l^2 sf2),
+ *      J = argmax_j k_j (lowest index on ties).
+ * tmp: hits [1 + rays] int32, rays = ((u1 - u0) / stride + 1) ((v1 - v0) / stride + 1): the crossings, compacted through an
+ *      integer counter; their order reaches no output.
+ * Three launches (fill, march, variance; two without Kinv).  No float atomics: every output is a function of its own pixel
+ * alone and comes out the same bits on every call.  Accuracy against the fp64 reference: tests/test_gpu_gpis.py. */
+typedef struct TgsGpisView {
+  float R[9];
+  float t[3];
+  float fx, fy, cx, cy;
+  int32_t W, H;
+  int32_t u0, v0, u1, v1, stride;
+  float z_lo, dz;
+  int32_t n_steps;
+  float max_var, var_floor;
+} TgsGpisView;
+int tgs_gpis_render(int n, const float* X, int n_p, const float* P, const float* N, const double* Kinv /*may be NULL*/,
+                    float l, float sf2, float prior, const TgsGpisView* view, float* depth, float* var /*may be NULL*/,
+                    float* normal /*may be NULL*/, int32_t* hits, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

@@ -9,7 +9,13 @@ touch_gs_amd.prepare), the reference's bunny_real flag set, 8 training views of 
                           centre's hit, rotated into the camera's OpenCV axes), written as gt_normal/<stem>.npy (float16):
                           the best prior there can be -- an upper bound on what a GPIS-gradient or monocular normal map gives
 
-Both runs are evaluated by run_eval under IS_REAL_WORLD on the held-out views (psnr, gt_depth_mse against the sensor),
+    touch_plus_gpis_normals   (--gpis-normals only) the same with the priors a capture can actually have: the GPIS surface
+                          normals of the touches themselves, rendered by GPIS.render_depth(backend="hip", return_normals=True)
+                          into normals_gpis/<stem>.npy with conf = clip(1 - var / gpis_max_var, 0, 1).  They
+                          exist on the touched patches only.  The result goes to profiles/gpis_normal_quality.json; the two
+                          arms above compute what they compute without the flag.
+
+All runs are evaluated by run_eval under IS_REAL_WORLD on the held-out views (psnr, gt_depth_mse against the sensor),
 against the analytic depth (exact_depth_mse) and against the exact normals (normal_angle_deg: the conf-weighted mean angle
 between the normals of the rendered depth and the prior over the supervised centres).  Report only: no threshold is set;
 whichever way the comparison comes out, the numbers are written as measured.
@@ -31,8 +37,11 @@ ap.add_argument("--width", type=int, default=1280)
 ap.add_argument("--iters", type=int, default=30000)
 ap.add_argument("--num-gaussians", type=int, default=100000)
 ap.add_argument("--normal-mult", type=float, default=0.05)
-ap.add_argument("--out", default=os.path.join("profiles", "normal_prior_quality.json"))
+ap.add_argument("--gpis-normals", action="store_true", help="add the touch_plus_gpis_normals arm")
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join("profiles", "gpis_normal_quality.json" if args.gpis_normals else "normal_prior_quality.json")
 if not torch.cuda.is_available():
     raise SystemExit("tools/normal_prior_quality.py trains: it needs the GPU")
 root = args.root or tempfile.mkdtemp(prefix="npq_")
@@ -60,7 +69,12 @@ if not os.path.exists(os.path.join(root, "gt_normal")):
         np.save(os.path.join(root, "gt_normal", os.path.splitext(os.path.basename(fr["file_path"]))[0] + ".npy"), n.astype(np.float16))
     out["normals_s"] = round(time.perf_counter() - t, 1)
 
+if args.gpis_normals and not os.path.exists(os.path.join(root, "normals_gpis")):
+    out["gpis_normals"] = A.write_gpis_normals(root)
+
 RUNS = {"touch_only": [], "touch_plus_normals": ["--normal-dir", "gt_normal", "--normal-mult", str(args.normal_mult)]}
+if args.gpis_normals:
+    RUNS["touch_plus_gpis_normals"] = ["--normal-dir", "normals_gpis", "--normal-mult", str(args.normal_mult)]
 KEYS = ("psnr", "ssim", "depth_mse", "gt_depth_mse", "gt_object_depth_mse", "exact_depth_mse", "exact_object_depth_mse",
         "gt_depth_mse_m2", "exact_depth_mse_m2", "exact_depth_median_abs_m", "exact_object_depth_median_abs_m")
 out["runs"] = {}

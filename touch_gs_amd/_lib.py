@@ -42,6 +42,14 @@ class TgsAdamSpec(C.Structure):
                 ("bias_corr1", C.c_float), ("bias_corr2", C.c_float), ("device_bias_corr", C.c_void_p)]
 
 
+class TgsGpisView(C.Structure):
+    """One view of tgs_gpis_render (tgs.h): camera, region of interest, march."""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("u0", C.c_int32), ("v0", C.c_int32), ("u1", C.c_int32),
+                ("v1", C.c_int32), ("stride", C.c_int32), ("z_lo", C.c_float), ("dz", C.c_float), ("n_steps", C.c_int32),
+                ("max_var", C.c_float), ("var_floor", C.c_float)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 # name -> (restype, argtypes); must list every symbol declared in include/tgs.h
@@ -106,6 +114,7 @@ SIGNATURES = {
                                               _P, _P, _P, _P, _P, _P]),
     "tgs_depth_normal_fwd_bwd": (C.c_int, [C.POINTER(TgsCamera), _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P,
                                           _P, _I, _P]),
+    "tgs_gpis_render": (C.c_int, [_I, _P, _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.POINTER(TgsGpisView), _P, _P, _P, _P, _P]),
     "tgs_peer_alloc": (C.c_int, [C.c_size_t, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "tgs_peer_open": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]),
     "tgs_peer_close": (C.c_int, [_P]),

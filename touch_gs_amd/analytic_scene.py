@@ -249,9 +249,13 @@ def fake_monocular_depth(gt: np.ndarray, rng: np.random.Generator) -> np.ndarray
 def write_raw_capture(root: str, n_views: int = 100, n_touches: int = 50, W: int = 1280, H: int = 720,
                       device="cpu", seed: int = 0, gpis_stride: int = 2, gpis_length_scale: float = 0.02, gpis_max_var: float = 0.01,
                       sensor_noise_mm: float = 1.0, verbose: bool = False, with_gpis: bool = True,
-                      gpis_max_points: int = 1300) -> dict:
+                      gpis_max_points: int = 1300, gpis_backend: Optional[str] = None, gpis_normals: bool = False) -> dict:
     """Writes the raw capture described in the module docstring.  ``W, H`` scale the reference's 1280 x 720 camera
-    (intrinsics scale along).  Returns a summary (touch point count, GPIS error against the analytic surface)."""
+    (intrinsics scale along).  Returns a summary (touch point count, GPIS error against the analytic surface).
+    ``gpis_backend``: ``GPIS.render_depth``'s backend (None = NumPy / torch on ``device``, "hip" = the HIP kernels on the
+    current device).  ``gpis_normals``: also writes ``normals_gpis/<image stem>.npy`` (float32 [H,W,3], the GPIS surface normal
+    in the view's OpenCV camera axes, 0 = none) and ``normals_gpis/<image stem>_conf.npy`` (conf = clip(1 - var /
+    gpis_max_var, 0, 1)): the files ``dataset.Scene(normal_dir="normals_gpis")`` / ``--normal-dir`` read."""
     from PIL import Image
     from .gpis import GPIS, estimate_outward_normals
     from .plumbing import write_png16, to_uint16_mm
@@ -261,7 +265,8 @@ def write_raw_capture(root: str, n_views: int = 100, n_touches: int = 50, W: int
     intr = tuple(v * k for v in TRAIN_INTRINSICS)
     s_intr = tuple(v * k for v in SENSOR_INTRINSICS)
     sW, sH = int(round(SENSOR_SIZE[0] * k)), int(round(SENSOR_SIZE[1] * k))
-    for d in ("imgs", "realsense_depth", "gpis_depth", "gpis_var", "zoe_depth", "gt_depth", "gt_object_mask"):
+    for d in ("imgs", "realsense_depth", "gpis_depth", "gpis_var", "zoe_depth", "gt_depth", "gt_object_mask") \
+            + (("normals_gpis",) if gpis_normals else ()):
         os.makedirs(os.path.join(root, d), exist_ok=True)
     cams = orbit_cameras(n_views, seed=seed)
     pts, sens = touch_readings(sc, n_touches, seed=seed)
@@ -289,17 +294,31 @@ def write_raw_capture(root: str, n_views: int = 100, n_touches: int = 50, W: int
         np.save(os.path.join(root, "realsense_depth", f"{stem(i)}.npy"), np.where(rs > 0, rs_mm, 0.0))
         tm["io"] += clock() - t0
         t0 = clock()
-        if with_gpis:
+        gn = None
+        if with_gpis and (gpis_backend is not None or gpis_normals):
+            out = gp.render_depth(c2w, *intr, W, H, near=0.05, far=1.5, stride=gpis_stride, max_var=gpis_max_var,
+                                  var_floor=1e-3, roi_margin_px=max(int(24 * k), 4), backend=gpis_backend,
+                                  return_normals=gpis_normals)
+            gd, gv = out[0], out[1]
+            if gpis_normals:   # (NaN = none while the holes of the stride are filled, 0 = none in the file)
+                gn = np.where(np.isfinite(gd)[..., None], out[2], np.nan)
+        elif with_gpis:
             gd, gv = gp.render_depth(c2w, *intr, W, H, near=0.05, far=1.5, stride=gpis_stride, max_var=gpis_max_var,
                                       var_floor=1e-3, roi_margin_px=max(int(24 * k), 4))
         else:
             gd = gv = np.full((H, W), np.nan)
+        if gpis_normals and gn is None:
+            gn = np.full((H, W, 3), np.nan)
         if gpis_stride > 1:   # rendered on a coarser grid: fill the skipped pixels from the nearest rendered one
             gd, gv = _fill_stride(gd, gpis_stride), _fill_stride(gv, gpis_stride)
+            if gpis_normals:
+                gn = np.stack([_fill_stride(gn[..., a], gpis_stride) for a in range(3)], -1)
         tm["gpis"] += clock() - t0
         t0 = clock()
         np.save(os.path.join(root, "gpis_depth", f"Image{stem(i)}.npy"), gd)
         np.save(os.path.join(root, "gpis_var", f"Image{stem(i)}.npy"), gv)
+        if gpis_normals:
+            _save_gpis_normals(root, stem(i), gn, gv, gpis_max_var)
         write_png16(os.path.join(root, "zoe_depth", f"{stem(i)}.png"), to_uint16_mm(fake_monocular_depth(r["depth"], rng)))
         m = np.isfinite(gd) & r["object"]
         if m.any():
@@ -317,6 +336,42 @@ def write_raw_capture(root: str, n_views: int = 100, n_touches: int = 50, W: int
                 gpis_rmse_m=float(np.mean(err)) if err else None, gpis_object_cover=float(np.mean(cover)) if cover else 0.0,
                 intrinsics=intr, sensor_intrinsics=s_intr, sensor_size=(sW, sH),
                 seconds={k: round(v, 1) for k, v in tm.items()})
+
+
+def _save_gpis_normals(root: str, stem: str, gn: np.ndarray, gv: np.ndarray, gpis_max_var: float):
+    """normals_gpis/<stem>.npy (NaN -> 0 = no prior) and <stem>_conf.npy = clip(1 - var / gpis_max_var, 0, 1)."""
+    np.save(os.path.join(root, "normals_gpis", f"{stem}.npy"), np.nan_to_num(gn, nan=0.0).astype(np.float32))
+    conf = np.clip(1.0 - np.nan_to_num(gv, nan=gpis_max_var) / gpis_max_var, 0.0, 1.0)
+    np.save(os.path.join(root, "normals_gpis", f"{stem}_conf.npy"), conf.astype(np.float32))
+
+
+def write_gpis_normals(root: str, n_touches: int = 50, seed: int = 0, gpis_stride: int = 2, gpis_length_scale: float = 0.02,
+                       gpis_max_var: float = 0.01, gpis_max_points: int = 1300, gpis_backend: Optional[str] = "hip") -> dict:
+    """``normals_gpis/`` for a raw capture that :func:`write_raw_capture` wrote WITHOUT ``gpis_normals``: the same touches
+    and the same fit (pass the capture's arguments), every frame of its transforms.json rendered again with normals.
+    Nothing else in the capture is touched.  -> {"views", "seconds"}."""
+    import time
+    from .gpis import GPIS, estimate_outward_normals
+    with open(os.path.join(root, "transforms.json")) as f:
+        meta = json.load(f)
+    W, H = int(meta["w"]), int(meta["h"])
+    intr = (meta["fl_x"], meta["fl_y"], meta["cx"], meta["cy"])
+    k = W / 1280.0
+    pts, sens = touch_readings(AnalyticScene("cpu"), n_touches, seed=seed)
+    gp = GPIS(length_scale=gpis_length_scale, offset=0.005, noise_var=1e-5).fit(
+        pts, estimate_outward_normals(pts, sens), max_points=gpis_max_points, rng=np.random.default_rng(seed))
+    os.makedirs(os.path.join(root, "normals_gpis"), exist_ok=True)
+    t0 = time.perf_counter()
+    for fr in meta["frames"]:
+        gd, gv, gn = gp.render_depth(np.array(fr["transform_matrix"]), *intr, W, H, near=0.05, far=1.5, stride=gpis_stride,
+                                     max_var=gpis_max_var, var_floor=1e-3, roi_margin_px=max(int(24 * k), 4),
+                                     backend=gpis_backend, return_normals=True)
+        gn = np.where(np.isfinite(gd)[..., None], gn, np.nan)
+        if gpis_stride > 1:
+            gv = _fill_stride(gv, gpis_stride)
+            gn = np.stack([_fill_stride(gn[..., a], gpis_stride) for a in range(3)], -1)
+        _save_gpis_normals(root, os.path.splitext(os.path.basename(fr["file_path"]))[0], gn, gv, gpis_max_var)
+    return dict(views=len(meta["frames"]), seconds=round(time.perf_counter() - t0, 1))
 
 
 def _fill_stride(a: np.ndarray, stride: int) -> np.ndarray:
