@@ -686,6 +686,70 @@ int tgs_gpis_render(int n, const float* X, int n_p, const float* P, const float*
                     float l, float sf2, float prior, const TgsGpisView* view, float* depth, float* var /*may be NULL*/,
                     float* normal /*may be NULL*/, int32_t* hits, void* stream);
 
+/* TSDF fusion of depth images into a voxel grid, and the grid's zero crossings as an oriented, coloured point cloud
+ *     (an ADDITION within TGS_VERSION 320: a new struct and three new calls, nothing earlier changes; csrc/tsdf.hip,
+ *     DESIGN 5.1k).  The definition is tests/tsdf_ref.py (fp64 NumPy); touch_gs_amd.tsdf.TsdfVolume is the caller.
+ * GRID: nx x ny x nz voxels of side vox, x fastest in memory (voxel (i, j, k) at i + nx (j + ny k)), at most 2^29 - 1 of
+ *      them.  Voxel (i, j, k) has its centre at ((i + 1/2) vox, (j + 1/2) vox, (k + 1/2) vox) in GRID-LOCAL coordinates, formed
+ *      in fp32 from the indices themselves.  The grid's world origin never reaches the device: the caller forms each view's
+ *      R (world -> camera, OpenCV axes, row-major) and t' = R origin + t in fp64 and rounds them once (the re-centring of
+ *      tgs_gpis_render), so a scene far from the world origin loses no digits.
+ * STATE: sums, not a running average, all fp32:  S [V] = sum w d,  Wt [V] = sum w,  C [V,3] = sum w rgb (may be NULL).  The
+ *      TSDF value is f = S / Wt.  The caller zeroes them once; each call adds to them.
+ * tgs_tsdf_integrate: 1 <= n_views <= 8 views per launch, `views` a HOST array (the structs travel as kernel arguments).
+ *      A view: R, t (= t' above), fx, fy, cx, cy, W, H, near_plane, pix_center (pixel (x, y) has its centre at
+ *      (x + pix_center, y + pix_center), as TgsCamera), and three DEVICE pointers: depth [H,W], weight [H,W] or NULL (= 1
+ *      everywhere), rgb [H,W,3] or NULL (the view adds no colour).  The depth is CAMERA-SPACE z, what the rasterizer renders:
+ *      K1 stores a Gaussian's depth as  R[6..8] . mean + t[2]  (csrc/project.hip, geom_eval: G.tz, splat slot 2) and K6
+ *      composites that, so depth_acc / alpha -- and the median depth, which is one Gaussian's -- is z, not the distance
+ *      along the ray.
+ *      For each voxel, and each view in array order, with c the voxel's centre:
+ *        p = R c + t;                                         skip the view if p.z <= near_plane
+ *        u = fx p.x / p.z + cx,  v = fy p.y / p.z + cy;       pixel = (floor(u + 1/2 - pix_center), floor(v + 1/2 - pix_center)):
+ *                                                             the NEAREST pixel, no interpolation across depth edges;
+ *                                                             skip if it lies outside the image
+ *        D = depth[pixel];                                    skip unless D is finite and > 0
+ *        w = weight[pixel] (1 if NULL);                       skip unless w is finite and > 0
+ *        sdf = D - p.z;                                       skip if sdf < -trunc
+ *        d = min(sdf / trunc, 1);  S += w d;  Wt += w;  C += w rgb[pixel]
+ *      Every product and sum rounds on its own (no contraction), in the order written.  One launch; every voxel is read and
+ *      written once by the one lane that owns it, whatever n_views is: no atomics, and the sequence of fp32 operations on a
+ *      voxel is the same whether eight views arrive in one call or in eight -- batching cannot be seen in the bits.
+ * tgs_tsdf_extract_count: a voxel is VALID iff Wt >= w_min (w_min > 0).  For voxel a and its +x, +y, +z neighbour b the edge
+ *      is a CROSSING iff both are valid and (f_a < 0) != (f_b < 0).  counts [V] int32 = the crossings of a, 0 ... 3.
+ * tgs_tsdf_extract_points: offsets [V] int64 = the exclusive prefix sum of counts (the caller's; the rows must hold its
+ *      total).  Crossing m of voxel a, in axis order, lands in row offsets[a] + m: the output order is a function of the grid
+ *      alone.  Per crossing on axis k:
+ *        t = f_a / (f_a - f_b)                                (the ends differ in sign: no cancellation)
+ *        point  = centre_a + t vox e_k                        grid-local, fp32
+ *        g(v)_m = central difference of f along axis m where both neighbours of v are valid, one-sided where exactly one
+ *                 is, 0 otherwise (a voxel outside the grid is not valid)
+ *        normal = normalize((1 - t) g(a) + t g(b)),           exactly 0 if that length is 0 or not finite; OUTWARD, because f
+ *                                                             grows towards the observer
+ *        colour = (1 - t) C_a / Wt_a + t C_b / Wt_b           (colors may be NULL; needs C)
+ *        edge_id = 3 a + k, int64                             (may be NULL)
+ *      points, normals, colors [total,3] fp32.
+ * Every argument is checked before any launch (TGS_E_ARG and a tgs_last_error text): NULL required pointers, n_views outside
+ * 1 ... 8, non-positive dims, vox, trunc or w_min, a view without depth or with a bad size / intrinsics / near plane, more
+ * voxels than the 32-bit index holds.  Accuracy against the fp64 reference: tests/test_gpu_tsdf.py. */
+typedef struct TgsTsdfView {
+  float R[9];
+  float t[3];
+  float fx, fy, cx, cy;
+  int32_t W, H;
+  float near_plane, pix_center;
+  const float* depth;
+  const float* weight;
+  const float* rgb;
+} TgsTsdfView;
+int tgs_tsdf_integrate(int nx, int ny, int nz, float vox, float trunc, float* S, float* Wt, float* C /*may be NULL*/,
+                       int n_views, const TgsTsdfView* views, void* stream);
+int tgs_tsdf_extract_count(int nx, int ny, int nz, float vox, const float* S, const float* Wt, float w_min, int32_t* counts,
+                           void* stream);
+int tgs_tsdf_extract_points(int nx, int ny, int nz, float vox, const float* S, const float* Wt, const float* C /*may be NULL*/,
+                            float w_min, const int64_t* offsets, float* points, float* normals, float* colors /*may be NULL*/,
+                            int64_t* edge_id /*may be NULL*/, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

@@ -50,6 +50,13 @@ class TgsGpisView(C.Structure):
                 ("max_var", C.c_float), ("var_floor", C.c_float)]
 
 
+class TgsTsdfView(C.Structure):
+    """One view of tgs_tsdf_integrate (tgs.h): re-centred camera and the device pointers of its images."""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("near_plane", C.c_float), ("pix_center", C.c_float),
+                ("depth", C.c_void_p), ("weight", C.c_void_p), ("rgb", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 # name -> (restype, argtypes); must list every symbol declared in include/tgs.h
@@ -115,6 +122,9 @@ SIGNATURES = {
     "tgs_depth_normal_fwd_bwd": (C.c_int, [C.POINTER(TgsCamera), _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P,
                                           _P, _I, _P]),
     "tgs_gpis_render": (C.c_int, [_I, _P, _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.POINTER(TgsGpisView), _P, _P, _P, _P, _P]),
+    "tgs_tsdf_integrate": (C.c_int, [_I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, C.POINTER(TgsTsdfView), _P]),
+    "tgs_tsdf_extract_count": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, C.c_float, _P, _P]),
+    "tgs_tsdf_extract_points": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     "tgs_peer_alloc": (C.c_int, [C.c_size_t, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "tgs_peer_open": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]),
     "tgs_peer_close": (C.c_int, [_P]),

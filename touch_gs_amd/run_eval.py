@@ -22,17 +22,10 @@ import os
 import torch
 
 
-def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False,
-             normals: bool = False, normal_dir=None, normal_frame=None) -> dict:
-    """Rebuild the model of one training run from its config.json + newest checkpoint and evaluate
-    it on the run's eval split.  ``depth_stats``: the results gain median_depth_mse / gt_depth_mse_median /
-    gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views).  ``normals``: the
-    results gain normal_angle_deg (against the run's own normal priors, or those of ``normal_dir`` / ``normal_frame`` if
-    given) and the render dump normal/."""
-    from .dataset import Scene
+def load_model(run_dir: str, device="cuda"):
+    """(model, config dict, checkpoint path): the model of one training run rebuilt from its config.json + newest checkpoint."""
     from .model import DepthGaussianSplattingModel, ModelConfig
     from .optim import GaussianParams
-    from .train import evaluate, render_views
     with open(os.path.join(run_dir, "config.json")) as f:
         cfg = json.load(f)
     ckpts = sorted(glob.glob(os.path.join(run_dir, "step-*.ckpt")))
@@ -43,6 +36,21 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
     mc["background_color"] = tuple(mc.get("background_color", (0.0, 0.0, 0.0)))
     model = DepthGaussianSplattingModel(ModelConfig(**mc), GaussianParams.allocate(sd["N"], sd["K"], device))
     model.load_state_dict(sd)
+    return model, cfg, ckpts[-1]
+
+
+def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False,
+             normals: bool = False, normal_dir=None, normal_frame=None, surface: bool = False) -> dict:
+    """Rebuild the model of one training run from its config.json + newest checkpoint and evaluate
+    it on the run's eval split.  ``depth_stats``: the results gain median_depth_mse / gt_depth_mse_median /
+    gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views).  ``normals``: the
+    results gain normal_angle_deg (against the run's own normal priors, or those of ``normal_dir`` / ``normal_frame`` if
+    given) and the render dump normal/.  ``surface``: the run's surface is exported beside the results
+    (touch_gs_amd.export.export_tsdf with its defaults -> ``<out_json stem>_surface/``) and, when the capture has ground truth
+    (``gt_depth/``), the results gain surface_chamfer / surface_precision / surface_recall / surface_fscore."""
+    from .dataset import Scene
+    from .train import evaluate, render_views
+    model, cfg, ckpt = load_model(run_dir, device)
     if cfg.get("synthetic"):
         from .scene import make_view
         N, W, H = cfg["synthetic"]
@@ -56,10 +64,19 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
         views, names, scale = [scene.views[i] for i in idx], [scene.names[i] for i in idx], scene.scale
     results = evaluate(model, views, depth_stats=depth_stats, normals=normals)
     results.setdefault("lpips", float("nan"))   # get_results.py:38 indexes it unconditionally
+    if surface:
+        if cfg.get("synthetic"):
+            raise ValueError("--surface needs a run trained on a capture")
+        from .export import export_tsdf
+        info = export_tsdf(run_dir, os.path.splitext(os.path.abspath(out_json))[0] + "_surface", device=device,
+                           loaded=(model, dict(cfg, checkpoint=ckpt), scene))
+        for k in ("chamfer", "precision", "recall", "fscore"):
+            if "surface_metrics" in info:
+                results["surface_" + k] = info["surface_metrics"][k]
     os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
     with open(out_json, "w") as f:
         json.dump({"experiment_name": os.path.basename(os.path.dirname(os.path.dirname(run_dir))),
-                   "method_name": "depth-gaussian-splatting", "checkpoint": ckpts[-1], "results": results}, f, indent=2)
+                   "method_name": "depth-gaussian-splatting", "checkpoint": ckpt, "results": results}, f, indent=2)
     if render_dir:
         render_views(model, views, render_dir, names, depth_stats=depth_stats, dataparser_scale=scale, normals=normals)
     return results
@@ -78,6 +95,9 @@ def main(argv=None):
     ap.add_argument("--normals", action="store_true",
                     help="also render the normals of the depth: normal/ PNGs ((n + 1) / 2, OpenCV camera axes) and, for runs "
                          "trained with --normal-dir, normal_angle_deg")
+    ap.add_argument("--surface", action="store_true",
+                    help="also export the run's surface (python -m touch_gs_amd.export tsdf, defaults) next to the results "
+                         "and, for a capture with gt_depth/, add surface_chamfer / _precision / _recall / _fscore")
     a = ap.parse_args(argv)
     full_exp_dir = os.path.join(a.output_dir, a.exp_name)
     os.makedirs(full_exp_dir, exist_ok=True)
@@ -88,7 +108,7 @@ def main(argv=None):
             continue
         out_json = os.path.join(full_exp_dir, f"{a.exp_name}_{len(done) + 1}.json")
         res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders", depth_stats=a.depth_stats,
-                       normals=a.normals)
+                       normals=a.normals, surface=a.surface)
         print(out_json, json.dumps(res))
         done.append(out_json)
         if len(done) == a.past_n_trials:
