@@ -528,13 +528,40 @@ def test_end_to_end_render_and_grads(dev, clamp):
         assert cos > 0.9999, (k, cos)
 
 
-def test_fused_loss_matches_autograd_path(dev):
-    """K7's in-kernel L1 + depth/uncertainty loss == the same loss applied through autograd."""
+def _tile_walks(cam, ts, fT):
+    """Per tile: how many entries of its list K7 walks = the deepest stop position among its pixels, at most the list."""
+    T = cam.num_tiles
+    TW, TH = cam.tiles
+    n = (ts[1:T + 1] - ts[:T]).long()
+    pad = torch.zeros(TH * 16, TW * 16, dtype=torch.int64, device=ts.device)
+    pad[:cam.H, :cam.W] = fT.stop_pos.long().clamp(max=int(n.max()))
+    return torch.minimum(pad.view(TH, 16, TW, 16).permute(0, 2, 1, 3).reshape(T, 256).max(1).values, n)
+
+
+@pytest.mark.parametrize("W,H", [(160, 96), (100, 70)])
+@pytest.mark.parametrize("form", ["one", "quad", "blocks", "f2b", "scan"])
+def test_fused_loss_matches_autograd_path(dev, form, W, H):
+    """K7's in-kernel L1 + depth/uncertainty loss == the same loss applied through autograd, through every form of K7
+    (they share one per-pixel prologue, pixel_upstream in raster.hip): one wave per tile, four waves (the (1, 8) rule:
+    every tile that walks more than 8 entries), 4x4 blocks, front to back, and the scan form beside the four-wave form
+    on the object-centric scene of test_k7_scan_form_on_the_longest_tiles.  100x70 has partial tiles on both edges.
+    The autograd reference runs with the process defaults, before a form is forced."""
     from touch_gs_amd import ops
-    N, W, H, deg = 3000, 160, 96, 3
-    P, cam = scene(N, W, H, deg, 51)
-    acam = amd_cam(cam)
-    D = to_dev(P, dev)
+    N, deg = 3000, 3
+    if form == "scan":
+        from touch_gs_amd.scene import make_camera, synthetic_gaussians
+        P, intr = synthetic_gaussians(N, W, H, deg, 5, clustered=True)
+        D = {k: v.to(dev).float().contiguous() for k, v in P.items()}
+        D["opac_logit"][::3] = 12.0                      # some opacities on the 0.999 clamp: both copies of the pixel loop run
+        acam = make_camera(intr, 1, 8, bg=(0.1, 0.2, 0.3))
+    else:
+        P, cam = scene(N, W, H, deg, 51)
+        acam = amd_cam(cam)
+        D = to_dev(P, dev)
+    opts = dict(one=ops.raster_opts(k7_quad=0, k7_blocks=0), blocks=ops.raster_opts(k7_blocks=1),
+                f2b=ops.raster_opts(k7_front_to_back=1)).get(form)
+    quad_rule = dict(quad=(1, 8), scan=(8, 16)).get(form)          # process-wide: (factor, min_walk) of tgs_set_k7_quad
+    scan_rule = (16, 512) if form == "scan" else None              # (scan_min, heads) of tgs_set_k7_scan
     g = torch.Generator().manual_seed(1)
     gt = torch.rand(H, W, 3, generator=g).to(dev)
     dgt = (torch.rand(H, W, generator=g) * 5)
@@ -547,20 +574,40 @@ def test_fused_loss_matches_autograd_path(dev):
         L = O.train_loss(dict(rgb=rgb, depth_acc=depth, alpha=alpha), gt, dgt, unc, ssim_lambda=0.0,
                          depth_loss_mult=0.3, depth_loss_type=loss_type, uncertainty_weight=uw)
         L.backward()
+        # fresh lists + ONE forward per backward: the walk statistics the chain-bound rule reads accumulate
         sp = ops.project_fwd(acam, D["means"], D["log_scales"], D["quats"], D["opac_logit"], D["sh"], deg)
         gb, ts, sg, st = ops.bin_sort(acam, sp)
         r2, d2, fT, fidx = ops.rasterize_fwd(acam, sp, sg, ts)
+        if quad_rule:      # the forced form does take tiles: the frame is chain-bound by the rule and some tile walks far enough
+            tmax = _tile_walks(acam, ts, fT)
+            assert int(tmax.max()) * 8192 > int(tmax.sum()) * quad_rule[0], (int(tmax.max()), int(tmax.sum()))
+            assert int((tmax > quad_rule[1]).sum()) > 0, int(tmax.max())
+            if scan_rule:
+                heads = ts.tile_order[:scan_rule[1]].long()
+                heads = heads[heads < acam.num_tiles]
+                assert int((tmax[heads] > max(scan_rule[0], quad_rule[1])).sum()) > 0, int(tmax[heads].max())
         cnt = int((dgt > 0).sum())
         spec = dict(gt_rgb=gt, gt_depth=dgt, uncertainty=unc if loss_type != "SIMPLE_LOSS" else None,
                     l1_weight=1.0 / (3 * H * W), depth_weight=0.3 / cnt, uncertainty_weight=uw, eps=1e-6)
-        partials, tl = ops.rasterize_bwd(acam, sp, gb, sg, ts, r2, d2, fT, loss=spec, want_tile_loss=True)
+        before_q, before_s = ops.set_k7_quad(), ops.set_k7_scan()
+        try:
+            if quad_rule:
+                ops.set_k7_quad(*quad_rule)
+            if scan_rule:
+                ops.set_k7_scan(*scan_rule)
+            partials, tl = ops.rasterize_bwd(acam, sp, gb, sg, ts, r2, d2, fT, loss=spec, want_tile_loss=True, opts=opts)
+        finally:
+            ops.set_k7_quad(*before_q)
+            ops.set_k7_scan(*before_s)
         vm, vls, vq, vol, vsh, _ = ops.project_bwd(acam, D["means"], D["log_scales"], D["quats"], D["opac_logit"],
                                                    D["sh"], deg, sp, gb, partials)
+        print(f"fused loss, {form} {W}x{H} {loss_type}: loss rel err {abs(tl.sum().item() - L.item()) / abs(L.item()):.2e}")
         assert abs(tl.sum().item() - L.item()) < 1e-4 * abs(L.item())
         for name, got in (("means", vm), ("log_scales", vls), ("quats", vq), ("opac_logit", vol), ("sh", vsh)):
             ref = Dg[name].grad
             scale = ref.abs().max().item()
-            assert (got - ref).abs().max().item() < 2e-4 * scale, (loss_type, name)
+            print(f"  {name}: max err / max magnitude {(got - ref).abs().max().item() / scale:.2e}")
+            assert (got - ref).abs().max().item() < 2e-4 * scale, (form, loss_type, name)
 
 
 def test_slot_ok_bitmaps_do_not_change_the_backward(dev, monkeypatch):

@@ -864,6 +864,179 @@ __device__ __forceinline__ size_t pair_index(const int32_t* __restrict__ group_b
          (size_t)((ty - y0) * w + (tx - x0));
 }
 
+// ---------------------------------------------------------------------------------------------
+// shared by the K7 forms: the forms differ in their WALK; prologue, reduction and record epilogue are these
+// ---------------------------------------------------------------------------------------------
+// pixel_upstream: the upstream gradient of pixel p (inside the image; Tf = its final transmittance): v_rgb / v_depth /
+// v_alpha as handed in, plus the gradient of the fused L1 and tactile depth / uncertainty loss.  WANT_LOSS: also add the
+// pixel's loss terms to l_l1 / l_dep (the forms that write tile_loss; the four-wave and scan forms leave the sums to
+// k_raster_bwd, which visits every tile).  A new loss term goes here, once.
+struct PixUpstream { float vCr, vCg, vCb, vD, vA; };
+// bg . v_C of it.  The forms have always rounded it in two ways (the compiler's choice of the product it fuses, which followed
+// the shape of each kernel); both are written out so that each form keeps its bits: the one-wave and block forms
+// fuse red into the rounded green product, the four-wave and scan forms green into the rounded red product.
+__device__ __forceinline__ float bg_dot_rg(const CamK& cam, const PixUpstream& u) {
+  return fmaf(cam.bg[2], u.vCb, fmaf(cam.bg[0], u.vCr, cam.bg[1] * u.vCg));
+}
+__device__ __forceinline__ float bg_dot_gr(const CamK& cam, const PixUpstream& u) {
+  return fmaf(cam.bg[2], u.vCb, fmaf(cam.bg[1], u.vCg, cam.bg[0] * u.vCr));
+}
+template <bool WANT_LOSS>
+__device__ __forceinline__ PixUpstream pixel_upstream(const LossK& loss, size_t p, float Tf, const float* __restrict__ out_rgb,
+                                                      const float* __restrict__ out_depth, const float* __restrict__ v_rgb,
+                                                      const float* __restrict__ v_depth, const float* __restrict__ v_alpha,
+                                                      float& l_l1, float& l_dep) {
+  PixUpstream u;
+  u.vCr = u.vCg = u.vCb = u.vD = 0.f;
+  u.vA = v_alpha ? v_alpha[p] : 0.f;
+  if (v_rgb) { u.vCr = v_rgb[3 * p]; u.vCg = v_rgb[3 * p + 1]; u.vCb = v_rgb[3 * p + 2]; }
+  if (v_depth) u.vD = v_depth[p];
+  if (loss.on) {
+    if (loss.gt_rgb) {
+      const float d0 = out_rgb[3 * p] - loss.gt_rgb[3 * p];
+      const float d1 = out_rgb[3 * p + 1] - loss.gt_rgb[3 * p + 1];
+      const float d2 = out_rgb[3 * p + 2] - loss.gt_rgb[3 * p + 2];
+      u.vCr += loss.l1w * ((d0 > 0.f) - (d0 < 0.f));
+      u.vCg += loss.l1w * ((d1 > 0.f) - (d1 < 0.f));
+      u.vCb += loss.l1w * ((d2 > 0.f) - (d2 < 0.f));
+      if constexpr (WANT_LOSS) l_l1 += loss.l1w * (fabsf(d0) + fabsf(d1) + fabsf(d2));
+    }
+    if (loss.gt_depth) {
+      const float gd = loss.gt_depth[p];
+      if (gd > 0.f) {
+        const float alpha = fmaxf(1.f - Tf, 1e-10f);
+        const float ia = 1.0f / alpha;
+        const float dhat = out_depth[p] * ia;
+        const float r = dhat - gd;
+        float wgt = loss.dw;
+        if (loss.unc) wgt = wgt / (loss.uw * loss.unc[p] + loss.eps);
+        if constexpr (WANT_LOSS) l_dep += wgt * r * r;
+        const float gdh = 2.f * wgt * r;
+        u.vD += gdh * ia;
+        // alpha is clamped from below: the clamp gates its gradient
+        if (1.f - Tf > 1e-10f) u.vA += -gdh * dhat * ia;
+      }
+    }
+  }
+  return u;
+}
+
+// the tile's two loss sums (L1, depth) of the lanes' l_l1 / l_dep
+__device__ __forceinline__ void store_tile_loss(float* __restrict__ tile_loss, int tile, int lane, float l_l1, float l_dep) {
+  if (tile_loss) {
+    const float a = wave_sum(l_l1), b = wave_sum(l_dep);
+    if (lane == 0) { tile_loss[2 * tile] = a; tile_loss[2 * tile + 1] = b; }
+  }
+}
+
+// The 64-lane reduction of one Gaussian's per-lane sums (quadrant forms: f2b, one wave, four waves).
+// Transposed reduction scratch `red` ([RED_ROWS][RED_RS] floats of LDS): row r holds the 64 lanes' values of per-lane accumulator r
+//   r = 0..2 v_rgb, 3 v_depth, 4 S = sum q, 5 Sx = sum q over the lane's right-hand pixels (slots 1, 3),
+//   6 Sy = sum q over its lower pixels (slots 2, 3), 7 Quv = sum q u v.
+// Reader lane (part, c) takes 16 consecutive lane values of row ROW[c] (writer lanes 16 part .. +15) and
+// forms a WEIGHTED sum: the pixel-coordinate moments the conversion to (v_xy, v_conic) needs are linear
+// in S, Sx, Sy with coefficients that depend on the writer lane only (u = u0 + 8 [right], v = v0 + 8
+// [lower], u0 = (l & 7) - 7.5, v0 = (l >> 3) - 7.5), so the blend loop accumulates 3 instead of 6
+// values per pixel slot and the moments appear here at the price of 16 FMAs instead of 15 adds:
+//   c  0..3  row 0..3, w = 1                          v_rgb, v_depth
+//   c  4     S, 1            -> Q0
+//   c  5, 6  S, u0 | Sx, 8   -> Qu  (sum of the two)
+//   c  7, 8  S, v0 | Sy, 8   -> Qv
+//   c  9,10  S, u0^2 | Sx, 16 u0 + 64   -> Quu
+//   c 11,12  S, v0^2 | Sy, 16 v0 + 64   -> Qvv
+//   c 13     Quv, 1
+// Bank conflicts: ds_read_b128 is served in lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32)
+// (MI355X_MICROARCH.md), NOT in quarter waves.  part = (lane >> 4) ^ [4 <= c < 12] makes every such group
+// read ONE part of <= 8 different rows, whose 68-float stride puts them on disjoint bank quads; lanes
+// l, l^16, l^32, l^48 still hold the four parts of one c, which is all the two folds need.
+constexpr int RED_RS = 68;
+constexpr int RED_ROWS = 8;
+struct RedTable { const float* rd; float wt[16]; };   // reader lane (part, c): where it reads in `red`, and its 16 weights
+__device__ __forceinline__ RedTable make_red_table(int lane, const float* red) {
+  RedTable t;
+  const int red_c = lane & 15;
+  const int red_part = (lane >> 4) ^ ((red_c >= 4 && red_c < 12) ? 1 : 0);
+  // row of term c, packed 4 bits each: c = 0 .. 15 -> 0 1 2 3 4 4 5 4 6 4 5 4 6 7 0 0
+  const unsigned long long ROWS = 0x0076454645443210ull;
+  t.rd = red + (int)((ROWS >> (4 * red_c)) & 15ull) * RED_RS + red_part * 16;
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const float u0 = (float)(i & 7) - 7.5f;
+    const float v0 = (float)(2 * red_part + (i >> 3)) - 7.5f;
+    float w = 1.f;                                   // c 0..4, 13
+    w = (red_c == 5) ? u0 : w;
+    w = (red_c == 7) ? v0 : w;
+    w = (red_c == 6 || red_c == 8) ? 8.f : w;
+    w = (red_c == 9) ? u0 * u0 : w;
+    w = (red_c == 11) ? v0 * v0 : w;
+    w = (red_c == 10) ? 16.f * u0 + 64.f : w;
+    w = (red_c == 12) ? 16.f * v0 + 64.f : w;
+    w = (red_c >= 14) ? 0.f : w;
+    t.wt[i] = w;
+  }
+  return t;
+}
+// One round: every lane scatters its 8 sums, reads back its weighted 16-lane part, two lane-swap folds, and lanes < 16
+// store the 14 totals of the Gaussian to sums_row ([16 slots], slot c < 14 = total of term c).
+// LDS operations of one wave execute in order, so the wave needs no barrier between the scatter and the transposed
+// read -- only the compiler must keep them in order (the fences).
+__device__ __forceinline__ void reduce_round(float* red, const RedTable& tab, int lane, const float (&acc)[RED_ROWS], float* sums_row) {
+#pragma unroll
+  for (int c = 0; c < RED_ROWS; c++) red[c * RED_RS + lane] = acc[c];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const float* wt = tab.wt;
+  const float4 r0 = ld4(tab.rd), r1 = ld4(tab.rd + 4), r2 = ld4(tab.rd + 8), r3 = ld4(tab.rd + 12);
+  // four independent chains of four
+  float o0 = r0.x * wt[0], o1 = r1.x * wt[4], o2 = r2.x * wt[8], o3 = r3.x * wt[12];
+  o0 = fmaf(r0.y, wt[1], o0); o1 = fmaf(r1.y, wt[5], o1); o2 = fmaf(r2.y, wt[9], o2); o3 = fmaf(r3.y, wt[13], o3);
+  o0 = fmaf(r0.z, wt[2], o0); o1 = fmaf(r1.z, wt[6], o1); o2 = fmaf(r2.z, wt[10], o2); o3 = fmaf(r3.z, wt[14], o3);
+  o0 = fmaf(r0.w, wt[3], o0); o1 = fmaf(r1.w, wt[7], o1); o2 = fmaf(r2.w, wt[11], o2); o3 = fmaf(r3.w, wt[15], o3);
+  float O = (o0 + o1) + (o2 + o3);
+  O = fold_xor16(O);
+  O = fold_xor32(O);
+  if (lane < 16) sums_row[lane] = O;
+  __builtin_amdgcn_wave_barrier();
+}
+
+// A Gaussian's tile totals -> its 48-B partial record P.  (gx, gy) = centre relative to the tile centre, (A, B, Cc) its
+// conic, Q* = the tile-centred moments of q, v_rgbd = {v_r, v_g, v_b, v_depth}.
+// v_sigma = -q, Delta = (gx - u, gy - v):  M* = sum v_sigma * Delta-monomials
+__device__ __forceinline__ void store_partial(float* __restrict__ partials, size_t P, float gx, float gy, float A, float B,
+                                              float Cc, float opac, float Q0, float Qu, float Qv, float Quu, float Qvv,
+                                              float Quv, float4 v_rgbd) {
+  const float Mx = -(gx * Q0 - Qu), My = -(gy * Q0 - Qv);
+  const float Mxx = -(gx * gx * Q0 - 2.f * gx * Qu + Quu);
+  const float Mxy = -(gx * gy * Q0 - gx * Qv - gy * Qu + Quv);
+  const float Myy = -(gy * gy * Q0 - 2.f * gy * Qv + Qvv);
+  float* o = partials + P * TGS_PARTIAL_FLOATS;
+  // {v_x, v_y, v_depth, v_opacity, v_a, v_b, v_c, v_r, v_g, v_b}
+  st4(o, make_float4(A * Mx + B * My, B * Mx + Cc * My, v_rgbd.w, Q0 / opac));
+  st4(o + 4, make_float4(0.5f * Mxx, Mxy, 0.5f * Myy, v_rgbd.x));
+  st4(o + 8, make_float4(v_rgbd.y, v_rgbd.z, 0.f, 0.f));
+}
+// the same for the quadrant forms' row of `sums`: s0 = {v_r, v_g, v_b, v_depth}  s1 = {Q0, Qu', Qu", Qv'}
+// s2 = {Qv", Quu', Quu", Qvv'}  s3 = {Qvv", Quv, -, -}  (a0 = {gx, gy, -, opacity}, a1 = conic: kept from staging)
+__device__ __forceinline__ void store_partial(float* __restrict__ partials, size_t P, float4 a0, float4 a1, float4 s0,
+                                              float4 s1, float4 s2, float4 s3) {
+  store_partial(partials, P, a0.x, a0.y, a1.x, a1.y, a1.z, a0.w, s1.x, s1.y + s1.z, s1.w + s2.x, s2.y + s2.z, s2.w + s3.x, s3.y, s0);
+}
+
+// Zero records for list positions first, first + stride, .. < end of tile (tx, ty): behind the last stop position
+// nothing received a gradient.  (first = that position + the thread's index, stride = the workgroup's size)
+__device__ __forceinline__ void zero_partials_behind(float* __restrict__ partials, const int32_t* __restrict__ group_base,
+                                                     const float* __restrict__ splats, const int32_t* __restrict__ sorted_gid,
+                                                     int tx, int ty, int first, int end, int stride) {
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = first; i < end; i += stride) {
+    const int gid = sorted_gid[i];
+    const size_t P = pair_index(group_base, gid, ld4(splats + (size_t)gid * TGS_SPLAT_FLOATS + 8), tx, ty);
+    float* o = partials + P * TGS_PARTIAL_FLOATS;
+    st4(o, z4); st4(o + 4, z4); st4(o + 8, z4);
+  }
+}
+
 __global__ __launch_bounds__(64) void k_raster_bwd_f2b(
     CamK cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ group_base,
     const int32_t* __restrict__ sorted_gid, const int32_t* __restrict__ tile_start,
@@ -899,98 +1072,23 @@ __global__ __launch_bounds__(64) void k_raster_bwd_f2b(
       const float Tf = final_T[p];
       const float o0 = out_rgb[3 * p], o1 = out_rgb[3 * p + 1], o2 = out_rgb[3 * p + 2];
       const float od = out_depth[p];
-      float vA = v_alpha ? v_alpha[p] : 0.f;
-      if (v_rgb) { vCr[k] = v_rgb[3 * p]; vCg[k] = v_rgb[3 * p + 1]; vCb[k] = v_rgb[3 * p + 2]; }
-      if (v_depth) vD[k] = v_depth[p];
-      if (loss.on) {
-        if (loss.gt_rgb) {
-          const float d0 = o0 - loss.gt_rgb[3 * p];
-          const float d1 = o1 - loss.gt_rgb[3 * p + 1];
-          const float d2 = o2 - loss.gt_rgb[3 * p + 2];
-          vCr[k] += loss.l1w * ((d0 > 0.f) - (d0 < 0.f));
-          vCg[k] += loss.l1w * ((d1 > 0.f) - (d1 < 0.f));
-          vCb[k] += loss.l1w * ((d2 > 0.f) - (d2 < 0.f));
-          l_l1 += loss.l1w * (fabsf(d0) + fabsf(d1) + fabsf(d2));
-        }
-        if (loss.gt_depth) {
-          const float gd = loss.gt_depth[p];
-          if (gd > 0.f) {
-            const float alpha = fmaxf(1.f - Tf, 1e-10f);
-            const float ia = 1.0f / alpha;
-            const float dhat = od * ia;
-            const float r = dhat - gd;
-            float wgt = loss.dw;
-            if (loss.unc) wgt = wgt / (loss.uw * loss.unc[p] + loss.eps);
-            l_dep += wgt * r * r;
-            const float gdh = 2.f * wgt * r;
-            vD[k] += gdh * ia;
-            // alpha is clamped from below: the clamp gates its gradient
-            if (1.f - Tf > 1e-10f) vA += -gdh * dhat * ia;
-          }
-        }
-      }
+      const PixUpstream u = pixel_upstream<true>(loss, p, Tf, out_rgb, out_depth, v_rgb, v_depth, v_alpha, l_l1, l_dep);
+      vCr[k] = u.vCr; vCg[k] = u.vCg; vCb[k] = u.vCb; vD[k] = u.vD;
       const float bgdot = cam.bg[0] * vCr[k] + cam.bg[1] * vCg[k] + cam.bg[2] * vCb[k];
       // colour part of the output without the background term, projected on v
       const float cvtot = vCr[k] * (o0 - Tf * cam.bg[0]) + vCg[k] * (o1 - Tf * cam.bg[1]) +
                           vCb[k] * (o2 - Tf * cam.bg[2]) + vD[k] * od;
-      XP[k] = Tf * (vA - bgdot) - cvtot;
+      XP[k] = Tf * (u.vA - bgdot) - cvtot;
     }
   }
-  if (tile_loss) {
-    const float a = wave_sum(l_l1), b = wave_sum(l_dep);
-    if (lane == 0) { tile_loss[2 * tile] = a; tile_loss[2 * tile + 1] = b; }
-  }
+  store_tile_loss(tile_loss, tile, lane, l_l1, l_dep);
   if (n == 0) return;
 
   __shared__ float4 recs[64 * 3];
-  __shared__ float4 sums[64 * 4];  // [Gaussian j][16 slots], slot c < 14 = total of term c (table below)
-  // Transposed reduction scratch: row r holds the 64 lanes' values of per-lane accumulator r
-  //   r = 0..2 v_rgb, 3 v_depth, 4 S = sum q, 5 Sx = sum q over the lane's right-hand pixels (slots 1, 3),
-  //   6 Sy = sum q over its lower pixels (slots 2, 3), 7 Quv = sum q u v.
-  // Reader lane (part, c) takes 16 consecutive lane values of row ROW[c] (writer lanes 16 part .. +15) and
-  // forms a WEIGHTED sum: the pixel-coordinate moments the conversion to (v_xy, v_conic) needs are linear
-  // in S, Sx, Sy with coefficients that depend on the writer lane only (u = u0 + 8 [right], v = v0 + 8
-  // [lower], u0 = (l & 7) - 7.5, v0 = (l >> 3) - 7.5), so the blend loop accumulates 3 instead of 6
-  // values per pixel slot and the moments appear here at the price of 16 FMAs instead of 15 adds:
-  //   c  0..3  row 0..3, w = 1                          v_rgb, v_depth
-  //   c  4     S, 1            -> Q0
-  //   c  5, 6  S, u0 | Sx, 8   -> Qu  (sum of the two)
-  //   c  7, 8  S, v0 | Sy, 8   -> Qv
-  //   c  9,10  S, u0^2 | Sx, 16 u0 + 64   -> Quu
-  //   c 11,12  S, v0^2 | Sy, 16 v0 + 64   -> Qvv
-  //   c 13     Quv, 1
-  // Bank conflicts: ds_read_b128 is served in lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32)
-  // (MI355X_MICROARCH.md), NOT in quarter waves.  part = (lane >> 4) ^ [4 <= c < 12] makes every such group
-  // read ONE part of <= 8 different rows, whose 68-float stride puts them on disjoint bank quads; lanes
-  // l, l^16, l^32, l^48 still hold the four parts of one c, which is all the two folds need.
-  constexpr int RED_RS = 68;
-  constexpr int RED_ROWS = 8;
+  __shared__ float4 sums[64 * 4];  // [Gaussian j][16 slots], slot c < 14 = total of term c (table at make_red_table)
   __shared__ float4 red4[RED_ROWS * RED_RS / 4];
   float* red = reinterpret_cast<float*>(red4);
-  const int red_c = lane & 15;
-  const int red_part = (lane >> 4) ^ ((red_c >= 4 && red_c < 12) ? 1 : 0);
-  float wt[16];
-  const float* red_rd;
-  {
-    // row of term c, packed 4 bits each: c = 0 .. 15 -> 0 1 2 3 4 4 5 4 6 4 5 4 6 7 0 0
-    const unsigned long long ROWS = 0x0076454645443210ull;
-    red_rd = red + (int)((ROWS >> (4 * red_c)) & 15ull) * RED_RS + red_part * 16;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const float u0 = (float)(i & 7) - 7.5f;
-      const float v0 = (float)(2 * red_part + (i >> 3)) - 7.5f;
-      float w = 1.f;                                   // c 0..4, 13
-      w = (red_c == 5) ? u0 : w;
-      w = (red_c == 7) ? v0 : w;
-      w = (red_c == 6 || red_c == 8) ? 8.f : w;
-      w = (red_c == 9) ? u0 * u0 : w;
-      w = (red_c == 11) ? v0 * v0 : w;
-      w = (red_c == 10) ? 16.f * u0 + 64.f : w;
-      w = (red_c == 12) ? 16.f * v0 + 64.f : w;
-      w = (red_c >= 14) ? 0.f : w;
-      wt[i] = w;
-    }
-  }
+  const RedTable tab = make_red_table(lane, red);
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   int base = start;
   for (; base < end; base += 64) {
@@ -1074,27 +1172,7 @@ __global__ __launch_bounds__(64) void k_raster_bwd_f2b(
           any |= okb;
         }
       }
-      if (any != 0ull) {
-        // LDS operations of one wave execute in order, so the (single-wave) workgroup needs no
-        // barrier between the scatter and the transposed read -- only the compiler must keep them
-        // in order, which the possible aliasing already forces
-#pragma unroll
-        for (int c = 0; c < RED_ROWS; c++) red[c * RED_RS + lane] = acc[c];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const float4 r0 = ld4(red_rd), r1 = ld4(red_rd + 4), r2 = ld4(red_rd + 8), r3 = ld4(red_rd + 12);
-        // four independent chains of four
-        float o0 = r0.x * wt[0], o1 = r1.x * wt[4], o2 = r2.x * wt[8], o3 = r3.x * wt[12];
-        o0 = fmaf(r0.y, wt[1], o0); o1 = fmaf(r1.y, wt[5], o1); o2 = fmaf(r2.y, wt[9], o2); o3 = fmaf(r3.y, wt[13], o3);
-        o0 = fmaf(r0.z, wt[2], o0); o1 = fmaf(r1.z, wt[6], o1); o2 = fmaf(r2.z, wt[10], o2); o3 = fmaf(r3.z, wt[14], o3);
-        o0 = fmaf(r0.w, wt[3], o0); o1 = fmaf(r1.w, wt[7], o1); o2 = fmaf(r2.w, wt[11], o2); o3 = fmaf(r3.w, wt[15], o3);
-        float O = (o0 + o1) + (o2 + o3);
-        O = fold_xor16(O);
-        O = fold_xor32(O);
-        if (lane < 16) reinterpret_cast<float*>(sums)[j * 16 + lane] = O;
-        __builtin_amdgcn_wave_barrier();
-      }
+      if (any != 0ull) reduce_round(red, tab, lane, acc, reinterpret_cast<float*>(sums) + j * 16);
     }
     };
     // The 0.999 clamp can only bind for opacity > 0.999; batches without a Gaussian above 0.99 (the
@@ -1103,31 +1181,10 @@ __global__ __launch_bounds__(64) void k_raster_bwd_f2b(
     if (__ballot(lane < cnt && a0.w > CLAMP_FREE_OPACITY) != 0ull) walk(std::true_type{});
     else walk(std::false_type{});
     __syncthreads();
-    if (lane < cnt) {
-      const float4 s0 = sums[lane * 4], s1 = sums[lane * 4 + 1], s2 = sums[lane * 4 + 2], s3 = sums[lane * 4 + 3];
-      // s0 = {v_r, v_g, v_b, v_depth}  s1 = {Q0, Qu', Qu", Qv'}  s2 = {Qv", Quu', Quu", Qvv'}  s3 = {Qvv", Quv, -, -}
-      const float gx = a0.x, gy = a0.y;           // centre relative to the tile centre (set while staging)
-      const float A = a1.x, B = a1.y, Cc = a1.z;
-      const float Q0 = s1.x, Qu = s1.y + s1.z, Qv = s1.w + s2.x, Quu = s2.y + s2.z, Qvv = s2.w + s3.x, Quv = s3.y;
-      // v_sigma = -q, Delta = (gx - u, gy - v):  M* = sum v_sigma * Delta-monomials
-      const float Mx = -(gx * Q0 - Qu), My = -(gy * Q0 - Qv);
-      const float Mxx = -(gx * gx * Q0 - 2.f * gx * Qu + Quu);
-      const float Mxy = -(gx * gy * Q0 - gx * Qv - gy * Qu + Quv);
-      const float Myy = -(gy * gy * Q0 - 2.f * gy * Qv + Qvv);
-      float* o = partials + P * TGS_PARTIAL_FLOATS;
-      // {v_x, v_y, v_depth, v_opacity, v_a, v_b, v_c, v_r, v_g, v_b}
-      st4(o, make_float4(A * Mx + B * My, B * Mx + Cc * My, s0.w, Q0 / a0.w));
-      st4(o + 4, make_float4(0.5f * Mxx, Mxy, 0.5f * Myy, s0.x));
-      st4(o + 8, make_float4(s0.y, s0.z, 0.f, 0.f));
-    }
+    if (lane < cnt) store_partial(partials, P, a0, a1, sums[lane * 4], sums[lane * 4 + 1], sums[lane * 4 + 2], sums[lane * 4 + 3]);
   }
   // every pixel of the tile has stopped: the rest of the list received no gradient
-  for (int i = base + lane; i < end; i += 64) {
-    const int gid = sorted_gid[i];
-    const size_t P = pair_index(group_base, gid, ld4(splats + (size_t)gid * TGS_SPLAT_FLOATS + 8), tx, ty);
-    float* o = partials + P * TGS_PARTIAL_FLOATS;
-    st4(o, z4); st4(o + 4, z4); st4(o + 8, z4);
-  }
+  zero_partials_behind(partials, group_base, splats, sorted_gid, tx, ty, base + lane, end, 64);
 }
 
 
@@ -1177,18 +1234,6 @@ __device__ __forceinline__ bool frame_is_chain_bound(const int32_t* __restrict__
 //     -- is k_raster_bwd_f2b's.  Batches behind the last pixel's stop position are never staged; their
 //     partial records are zero-filled up front.
 // (5 waves per SIMD -- amdgpu_waves_per_eu(5, 8): 96 VGPRs + 14 spilled -- 386 -> 508 us, same-box A/B: 112 VGPRs / 4 waves stay)
-#ifndef TGS_K7_FIRSTQ
-#define TGS_K7_FIRSTQ 0    // 1: the first quadrant a Gaussian reaches assigns its eight lane sums instead of clearing + accumulating (A/B switch: slower)
-#endif
-#ifndef TGS_K7_RECPF
-#define TGS_K7_RECPF 0     // 1: the next entry's staged record is read from LDS while the current entry is blended (A/B switch)
-#endif
-#ifndef TGS_K7_PAIR
-#define TGS_K7_PAIR 0      // 1: two Gaussians per reduction round (A/B switch; tools/build_variant.sh k7pair -DTGS_K7_PAIR=1)
-#endif
-#if TGS_K7_RECPF
-__attribute__((amdgpu_waves_per_eu(4, 8)))
-#endif
 __global__ __launch_bounds__(64) void k_raster_bwd(
     CamK cam, int T_total, const float* __restrict__ splats, const int32_t* __restrict__ group_base,
     const int32_t* __restrict__ sorted_gid, const int32_t* __restrict__ tile_start,
@@ -1225,44 +1270,12 @@ __global__ __launch_bounds__(64) void k_raster_bwd(
       const float Tf = final_T[p];
       T[k] = Tf;
       lim[k] = min(stop_pos[p], n);
-      float vA = v_alpha ? v_alpha[p] : 0.f;
-      if (v_rgb) { vCr[k] = v_rgb[3 * p]; vCg[k] = v_rgb[3 * p + 1]; vCb[k] = v_rgb[3 * p + 2]; }
-      if (v_depth) vD[k] = v_depth[p];
-      if (loss.on) {
-        if (loss.gt_rgb) {
-          const float d0 = out_rgb[3 * p] - loss.gt_rgb[3 * p];
-          const float d1 = out_rgb[3 * p + 1] - loss.gt_rgb[3 * p + 1];
-          const float d2 = out_rgb[3 * p + 2] - loss.gt_rgb[3 * p + 2];
-          vCr[k] += loss.l1w * ((d0 > 0.f) - (d0 < 0.f));
-          vCg[k] += loss.l1w * ((d1 > 0.f) - (d1 < 0.f));
-          vCb[k] += loss.l1w * ((d2 > 0.f) - (d2 < 0.f));
-          l_l1 += loss.l1w * (fabsf(d0) + fabsf(d1) + fabsf(d2));
-        }
-        if (loss.gt_depth) {
-          const float gd = loss.gt_depth[p];
-          if (gd > 0.f) {
-            const float alpha = fmaxf(1.f - Tf, 1e-10f);
-            const float ia = 1.0f / alpha;
-            const float dhat = out_depth[p] * ia;
-            const float r = dhat - gd;
-            float wgt = loss.dw;
-            if (loss.unc) wgt = wgt / (loss.uw * loss.unc[p] + loss.eps);
-            l_dep += wgt * r * r;
-            const float gdh = 2.f * wgt * r;
-            vD[k] += gdh * ia;
-            // alpha is clamped from below: the clamp gates its gradient
-            if (1.f - Tf > 1e-10f) vA += -gdh * dhat * ia;
-          }
-        }
-      }
-      const float bgdot = cam.bg[0] * vCr[k] + cam.bg[1] * vCg[k] + cam.bg[2] * vCb[k];
-      SX[k] = -Tf * (vA - bgdot);
+      const PixUpstream u = pixel_upstream<true>(loss, p, Tf, out_rgb, out_depth, v_rgb, v_depth, v_alpha, l_l1, l_dep);
+      vCr[k] = u.vCr; vCg[k] = u.vCg; vCb[k] = u.vCb; vD[k] = u.vD;
+      SX[k] = -Tf * (u.vA - bg_dot_rg(cam, u));
     }
   }
-  if (tile_loss) {
-    const float a = wave_sum(l_l1), b = wave_sum(l_dep);
-    if (lane == 0) { tile_loss[2 * tile] = a; tile_loss[2 * tile + 1] = b; }
-  }
+  store_tile_loss(tile_loss, tile, lane, l_l1, l_dep);
   if (n == 0) return;
   // per quadrant / per tile: how far into the list any pixel reaches (wave-uniform)
   int qlim[4];
@@ -1273,44 +1286,14 @@ __global__ __launch_bounds__(64) void k_raster_bwd(
   // written above
   if (tmax > quad.min_walk && frame_is_chain_bound(tile_start, T_total, quad)) return;   // (k_raster_bwd_quad's or k_raster_bwd_scan's)
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  // behind the last stop position nothing received a gradient
-  for (int i = start + tmax + lane; i < end; i += 64) {
-    const int gid = sorted_gid[i];
-    const size_t P = pair_index(group_base, gid, ld4(splats + (size_t)gid * TGS_SPLAT_FLOATS + 8), tx, ty);
-    float* o = partials + P * TGS_PARTIAL_FLOATS;
-    st4(o, z4); st4(o + 4, z4); st4(o + 8, z4);
-  }
+  zero_partials_behind(partials, group_base, splats, sorted_gid, tx, ty, start + tmax + lane, end, 64);
   if (tmax == 0) return;
 
   __shared__ float4 recs[64 * 3];
-  __shared__ float4 sums[64 * 4];  // [Gaussian j][16 slots], slot c < 14 = total of term c (table in k_raster_bwd_f2b)
-  constexpr int RED_RS = 68;
-  constexpr int RED_ROWS = 8;
-  __shared__ float4 red4[(TGS_K7_PAIR ? 2 : 1) * RED_ROWS * RED_RS / 4];
+  __shared__ float4 sums[64 * 4];  // [Gaussian j][16 slots], slot c < 14 = total of term c (table at make_red_table)
+  __shared__ float4 red4[RED_ROWS * RED_RS / 4];
   float* red = reinterpret_cast<float*>(red4);
-  const int red_c = lane & 15;
-  const int red_part = (lane >> 4) ^ ((red_c >= 4 && red_c < 12) ? 1 : 0);
-  float wt[16];
-  const float* red_rd;
-  {
-    const unsigned long long ROWS = 0x0076454645443210ull;
-    red_rd = red + (int)((ROWS >> (4 * red_c)) & 15ull) * RED_RS + red_part * 16;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const float u0 = (float)(i & 7) - 7.5f;
-      const float v0 = (float)(2 * red_part + (i >> 3)) - 7.5f;
-      float w = 1.f;                                   // c 0..4, 13
-      w = (red_c == 5) ? u0 : w;
-      w = (red_c == 7) ? v0 : w;
-      w = (red_c == 6 || red_c == 8) ? 8.f : w;
-      w = (red_c == 9) ? u0 * u0 : w;
-      w = (red_c == 11) ? v0 * v0 : w;
-      w = (red_c == 10) ? 16.f * u0 + 64.f : w;
-      w = (red_c == 12) ? 16.f * v0 + 64.f : w;
-      w = (red_c >= 14) ? 0.f : w;
-      wt[i] = w;
-    }
-  }
+  const RedTable tab = make_red_table(lane, red);
   for (int base = start + ((tmax - 1) & ~63); base >= start; base -= 64) {
     const int rel = base - start;
     const int cnt = min(64, tmax - rel);
@@ -1353,13 +1336,10 @@ __global__ __launch_bounds__(64) void k_raster_bwd(
       const int pos = rel + j;
       // acc: 0..2 v_rgb, 3 v_depth, 4 S = sum q, 5 Sx, 6 Sy, 7 Quv   (rows of the reduction scratch)
       any = 0ull;   // lanes with a contributing pixel, kept as a scalar mask (see k_raster_bwd_f2b)
-      // One quadrant of the Gaussian.  FIRST (TGS_K7_FIRSTQ, an experiment that LOST): the first quadrant a Gaussian
-      // reaches ASSIGNS the eight sums (w v instead of fma(w, v, 0): the same bits), which removes the eight v_mov that
-      // clear them -- 6 of ~86 VALU instructions per pair -- at the price of a four-way scalar switch and ten copies of
-      // this body instead of four: 383 -> 419 us (profiles/r5_ab_runs.txt).  Scalar branches are not free here.
-      auto quad = [&](auto KC, auto FC) {
+      // One quadrant of the Gaussian.  (Letting the first quadrant reached ASSIGN the eight sums instead of clearing
+      // them lost: 383 -> 419 us, profiles/r5_ab_runs.txt.)
+      auto quad = [&](auto KC) {
         constexpr int k = decltype(KC)::value;
-        constexpr bool FIRST = decltype(FC)::value;
         const float s = eval_s(qa, qb, pc, k);
         const float e = __builtin_amdgcn_exp2f(-s);
         const float al0 = MAYCLAMP ? fminf(ALPHA_MAX, e) : e;
@@ -1382,161 +1362,34 @@ __global__ __launch_bounds__(64) void k_raster_bwd(
         if constexpr (MAYCLAMP) q *= fmaxf(e * (1.0f / ALPHA_MAX), 1.0f);
         SX[k] += z;
         T[k] = Tp;
-        if constexpr (FIRST) {
-          acc[0] = w * vCr[k]; acc[1] = w * vCg[k]; acc[2] = w * vCb[k]; acc[3] = w * vD[k];
-          acc[4] = q;
-          acc[5] = (k & 1) ? q : 0.f;
-          acc[6] = (k >> 1) ? q : 0.f;
-          acc[7] = q * pc.uv[k];
-        } else {
-          acc[0] = fmaf(w, vCr[k], acc[0]); acc[1] = fmaf(w, vCg[k], acc[1]);
-          acc[2] = fmaf(w, vCb[k], acc[2]); acc[3] = fmaf(w, vD[k], acc[3]);
-          acc[4] += q;
-          if (k & 1) acc[5] += q;
-          if (k >> 1) acc[6] += q;
-          acc[7] = fmaf(q, pc.uv[k], acc[7]);
-        }
+        acc[0] = fmaf(w, vCr[k], acc[0]); acc[1] = fmaf(w, vCg[k], acc[1]);
+        acc[2] = fmaf(w, vCb[k], acc[2]); acc[3] = fmaf(w, vD[k], acc[3]);
+        acc[4] += q;
+        if (k & 1) acc[5] += q;
+        if (k >> 1) acc[6] += q;
+        acc[7] = fmaf(q, pc.uv[k], acc[7]);
         any |= gob;
       };
-#if TGS_K7_FIRSTQ
-      using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-      using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-      const std::true_type F{}; const std::false_type A{};
-      // a four-way scalar switch on the first quadrant (separate code per case: an `if (first)` inside one body is
-      // if-converted into eight more selects per quadrant)
-      switch (__builtin_ctz(m | 16u)) {
-        case 0: quad(I0{}, F); if (m & 2u) quad(I1{}, A); if (m & 4u) quad(I2{}, A); if (m & 8u) quad(I3{}, A); break;
-        case 1: quad(I1{}, F); if (m & 4u) quad(I2{}, A); if (m & 8u) quad(I3{}, A); break;
-        case 2: quad(I2{}, F); if (m & 8u) quad(I3{}, A); break;
-        case 3: quad(I3{}, F); break;
-        default:     // (cannot happen: the walk only visits entries with a quadrant bit) keep the sums defined
-#pragma unroll
-          for (int c = 0; c < RED_ROWS; c++) acc[c] = 0.f;
-      }
-#else
 #pragma unroll
       for (int c = 0; c < RED_ROWS; c++) acc[c] = 0.f;
-      if (m & 1u) quad(std::integral_constant<int, 0>{}, std::false_type{});
-      if (m & 2u) quad(std::integral_constant<int, 1>{}, std::false_type{});
-      if (m & 4u) quad(std::integral_constant<int, 2>{}, std::false_type{});
-      if (m & 8u) quad(std::integral_constant<int, 3>{}, std::false_type{});
-#endif
+      if (m & 1u) quad(std::integral_constant<int, 0>{});
+      if (m & 2u) quad(std::integral_constant<int, 1>{});
+      if (m & 4u) quad(std::integral_constant<int, 2>{});
+      if (m & 8u) quad(std::integral_constant<int, 3>{});
     };
-    // the weighted transposed sum of one Gaussian's 64 x 8 lane values out of `rd` (see the kernel's head comment)
-    auto reduce_rows = [&](const float* rd) {
-      const float4 r0 = ld4(rd), r1 = ld4(rd + 4), r2 = ld4(rd + 8), r3 = ld4(rd + 12);
-      float o0 = r0.x * wt[0], o1 = r1.x * wt[4], o2 = r2.x * wt[8], o3 = r3.x * wt[12];
-      o0 = fmaf(r0.y, wt[1], o0); o1 = fmaf(r1.y, wt[5], o1); o2 = fmaf(r2.y, wt[9], o2); o3 = fmaf(r3.y, wt[13], o3);
-      o0 = fmaf(r0.z, wt[2], o0); o1 = fmaf(r1.z, wt[6], o1); o2 = fmaf(r2.z, wt[10], o2); o3 = fmaf(r3.z, wt[14], o3);
-      o0 = fmaf(r0.w, wt[3], o0); o1 = fmaf(r1.w, wt[7], o1); o2 = fmaf(r2.w, wt[11], o2); o3 = fmaf(r3.w, wt[15], o3);
-      return (o0 + o1) + (o2 + o3);
-    };
-#if TGS_K7_RECPF
-    // (A/B switch) the NEXT entry's staged record is requested from LDS before the current entry is blended: its three
-    // broadcast ds_read_b128 are in flight under ~70 VALU instead of in front of them (+12 VGPRs: 124, still 4 waves / SIMD)
-    if (rem == 0ull) return;
-    int jn = 63 - __builtin_clzll(rem);
-    rem &= ~(1ull << jn);
-    float4 na = recs[jn * 3], nb = recs[jn * 3 + 1], nc = recs[jn * 3 + 2];
-    for (;;) {
-      const int j = jn;
-      const float4 qa = na, qb = nb, qc = nc;
-      const bool more = rem != 0ull;
-      if (more) {
-        jn = 63 - __builtin_clzll(rem);
-        rem &= ~(1ull << jn);
-        na = recs[jn * 3]; nb = recs[jn * 3 + 1]; nc = recs[jn * 3 + 2];
-      }
-      float acc[RED_ROWS];
-      unsigned long long any;
-      blend(j, qa, qb, qc, acc, any);
-      if (any != 0ull) {
-#pragma unroll
-        for (int c = 0; c < RED_ROWS; c++) red[c * RED_RS + lane] = acc[c];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float O = reduce_rows(red_rd);
-        O = fold_xor16(O);
-        O = fold_xor32(O);
-        if (lane < 16) reinterpret_cast<float*>(sums)[j * 16 + lane] = O;
-        __builtin_amdgcn_wave_barrier();
-      }
-      if (!more) break;
-    }
-#else
     while (rem) {
       const int j = 63 - __builtin_clzll(rem);
       rem &= ~(1ull << j);
       float acc[RED_ROWS];
       unsigned long long any;
       blend(j, recs[j * 3], recs[j * 3 + 1], recs[j * 3 + 2], acc, any);
-#if TGS_K7_PAIR
-      // Two Gaussians per reduction round (VERDICT r4 next #9a): the second one's blend runs before the first one's
-      // scatter -> transposed read round trip is waited for, and the two round trips overlap.  Same sums in the same
-      // order per Gaussian: bit-identical.  Costs 8 + ~16 VGPRs (3 waves per SIMD) and a second scratch image.
-      int j2 = -1;
-      float acc2[RED_ROWS];
-      unsigned long long any2 = 0ull;
-      if (rem) {
-        j2 = 63 - __builtin_clzll(rem);
-        rem &= ~(1ull << j2);
-        blend(j2, recs[j2 * 3], recs[j2 * 3 + 1], recs[j2 * 3 + 2], acc2, any2);
-      }
-      if (any != 0ull && any2 != 0ull) {
-#pragma unroll
-        for (int c = 0; c < RED_ROWS; c++) { red[c * RED_RS + lane] = acc[c]; red[RED_ROWS * RED_RS + c * RED_RS + lane] = acc2[c]; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float O = reduce_rows(red_rd), O2 = reduce_rows(red_rd + RED_ROWS * RED_RS);
-        O = fold_xor16(O); O2 = fold_xor16(O2);
-        O = fold_xor32(O); O2 = fold_xor32(O2);
-        if (lane < 16) { reinterpret_cast<float*>(sums)[j * 16 + lane] = O; reinterpret_cast<float*>(sums)[j2 * 16 + lane] = O2; }
-        __builtin_amdgcn_wave_barrier();
-        continue;
-      }
-      if (any2 != 0ull) {        // only the second one contributed: it takes the single path below
-#pragma unroll
-        for (int c = 0; c < RED_ROWS; c++) acc[c] = acc2[c];
-        any = any2;
-      }
-      const int jr = (any2 != 0ull) ? j2 : j;
-#else
-      const int jr = j;
-#endif
-      if (any != 0ull) {
-#pragma unroll
-        for (int c = 0; c < RED_ROWS; c++) red[c * RED_RS + lane] = acc[c];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float O = reduce_rows(red_rd);
-        O = fold_xor16(O);
-        O = fold_xor32(O);
-        if (lane < 16) reinterpret_cast<float*>(sums)[jr * 16 + lane] = O;
-        __builtin_amdgcn_wave_barrier();
-      }
+      if (any != 0ull) reduce_round(red, tab, lane, acc, reinterpret_cast<float*>(sums) + j * 16);
     }
-#endif
     };
     if (__ballot(lane < cnt && a0.w > CLAMP_FREE_OPACITY) != 0ull) walk(std::true_type{});
     else walk(std::false_type{});
     __syncthreads();
-    if (lane < cnt) {
-      const float4 s0 = sums[lane * 4], s1 = sums[lane * 4 + 1], s2 = sums[lane * 4 + 2], s3 = sums[lane * 4 + 3];
-      const float gx = a0.x, gy = a0.y;           // centre relative to the tile centre (set while staging)
-      const float A = a1.x, B = a1.y, Cc = a1.z;
-      const float Q0 = s1.x, Qu = s1.y + s1.z, Qv = s1.w + s2.x, Quu = s2.y + s2.z, Qvv = s2.w + s3.x, Quv = s3.y;
-      const float Mx = -(gx * Q0 - Qu), My = -(gy * Q0 - Qv);
-      const float Mxx = -(gx * gx * Q0 - 2.f * gx * Qu + Quu);
-      const float Mxy = -(gx * gy * Q0 - gx * Qv - gy * Qu + Quv);
-      const float Myy = -(gy * gy * Q0 - 2.f * gy * Qv + Qvv);
-      float* o = partials + P * TGS_PARTIAL_FLOATS;
-      st4(o, make_float4(A * Mx + B * My, B * Mx + Cc * My, s0.w, Q0 / a0.w));
-      st4(o + 4, make_float4(0.5f * Mxx, Mxy, 0.5f * Myy, s0.x));
-      st4(o + 8, make_float4(s0.y, s0.z, 0.f, 0.f));
-    }
+    if (lane < cnt) store_partial(partials, P, a0, a1, sums[lane * 4], sums[lane * 4 + 1], sums[lane * 4 + 2], sums[lane * 4 + 3]);
   }
 }
 
@@ -1598,13 +1451,7 @@ __global__ __launch_bounds__(64) void k_raster_bwd_blocks(
   const int ty = tile / cam.TW, tx = tile - ty * cam.TW;
   // lane -> pixel as in k_raster_fwd_blocks: DPP row g owns block (g & 1, g >> 1) of every quadrant
   const int g = lane >> 4, lx = 4 * (g & 1) + (lane & 3), ly = 4 * (g >> 1) + ((lane >> 2) & 3);
-  PixConst pc;
-  pc.u[0] = (float)lx - 7.5f; pc.u[1] = pc.u[0] + 8.f;
-  pc.v[0] = (float)ly - 7.5f; pc.v[1] = pc.v[0] + 8.f;
-#pragma unroll
-  for (int i = 0; i < 2; i++) { pc.uu[i] = pc.u[i] * pc.u[i]; pc.vv[i] = pc.v[i] * pc.v[i]; }
-#pragma unroll
-  for (int k = 0; k < 4; k++) pc.uv[k] = pc.u[k & 1] * pc.v[k >> 1];
+  const PixConst pc = make_pix_const(lx, ly);
   const int start = tile_start[tile], end = tile_start[tile + 1];
   const int n = end - start;
 
@@ -1622,43 +1469,12 @@ __global__ __launch_bounds__(64) void k_raster_bwd_blocks(
       const float Tf = final_T[p];
       T[k] = Tf;
       lim[k] = min(stop_pos[p], n);
-      float vA = v_alpha ? v_alpha[p] : 0.f;
-      if (v_rgb) { vCr[k] = v_rgb[3 * p]; vCg[k] = v_rgb[3 * p + 1]; vCb[k] = v_rgb[3 * p + 2]; }
-      if (v_depth) vD[k] = v_depth[p];
-      if (loss.on) {
-        if (loss.gt_rgb) {
-          const float d0 = out_rgb[3 * p] - loss.gt_rgb[3 * p];
-          const float d1 = out_rgb[3 * p + 1] - loss.gt_rgb[3 * p + 1];
-          const float d2 = out_rgb[3 * p + 2] - loss.gt_rgb[3 * p + 2];
-          vCr[k] += loss.l1w * ((d0 > 0.f) - (d0 < 0.f));
-          vCg[k] += loss.l1w * ((d1 > 0.f) - (d1 < 0.f));
-          vCb[k] += loss.l1w * ((d2 > 0.f) - (d2 < 0.f));
-          l_l1 += loss.l1w * (fabsf(d0) + fabsf(d1) + fabsf(d2));
-        }
-        if (loss.gt_depth) {
-          const float gd = loss.gt_depth[p];
-          if (gd > 0.f) {
-            const float alpha = fmaxf(1.f - Tf, 1e-10f);
-            const float ia = 1.0f / alpha;
-            const float dhat = out_depth[p] * ia;
-            const float r = dhat - gd;
-            float wgt = loss.dw;
-            if (loss.unc) wgt = wgt / (loss.uw * loss.unc[p] + loss.eps);
-            l_dep += wgt * r * r;
-            const float gdh = 2.f * wgt * r;
-            vD[k] += gdh * ia;
-            if (1.f - Tf > 1e-10f) vA += -gdh * dhat * ia;
-          }
-        }
-      }
-      const float bgdot = cam.bg[0] * vCr[k] + cam.bg[1] * vCg[k] + cam.bg[2] * vCb[k];
-      SX[k] = -Tf * (vA - bgdot);
+      const PixUpstream u = pixel_upstream<true>(loss, p, Tf, out_rgb, out_depth, v_rgb, v_depth, v_alpha, l_l1, l_dep);
+      vCr[k] = u.vCr; vCg[k] = u.vCg; vCb[k] = u.vCb; vD[k] = u.vD;
+      SX[k] = -Tf * (u.vA - bg_dot_rg(cam, u));
     }
   }
-  if (tile_loss) {
-    const float a = wave_sum(l_l1), b = wave_sum(l_dep);
-    if (lane == 0) { tile_loss[2 * tile] = a; tile_loss[2 * tile + 1] = b; }
-  }
+  store_tile_loss(tile_loss, tile, lane, l_l1, l_dep);
   if (n == 0) return;
   // how far into the list each of the 16 blocks reaches (wave-uniform: SGPRs), block of (row gg, quadrant k) = 4 (2 (k >> 1) + (gg >> 1)) + 2 (k & 1) + (gg & 1)
   int blim[16];
@@ -1673,12 +1489,7 @@ __global__ __launch_bounds__(64) void k_raster_bwd_blocks(
 #pragma unroll
   for (int b = 0; b < 16; b++) tmax = max(tmax, blim[b]);
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int i = start + tmax + lane; i < end; i += 64) {       // behind the last stop position nothing received a gradient
-    const int gid = sorted_gid[i];
-    const size_t P = pair_index(group_base, gid, ld4(splats + (size_t)gid * TGS_SPLAT_FLOATS + 8), tx, ty);
-    float* o = partials + P * TGS_PARTIAL_FLOATS;
-    st4(o, z4); st4(o + 4, z4); st4(o + 8, z4);
-  }
+  zero_partials_behind(partials, group_base, splats, sorted_gid, tx, ty, start + tmax + lane, end, 64);
   if (tmax == 0) return;
 
   __shared__ float4 recs[65 * 3];                 // 64 staged Gaussians + the null record (alpha = 0)
@@ -1796,17 +1607,8 @@ __global__ __launch_bounds__(64) void k_raster_bwd_blocks(
         s1.x += t1.x; s1.y += t1.y; s1.z += t1.z; s1.w += t1.w;
         s2.x += t2.x; s2.y += t2.y;
       }
-      const float gx = a0.x, gy = a0.y;
-      const float A = a1.x, B = a1.y, Cc = a1.z;
-      const float Q0 = s1.x, Qu = s1.y, Qv = s1.z, Quu = s1.w, Quv = s2.x, Qvv = s2.y;
-      const float Mx = -(gx * Q0 - Qu), My = -(gy * Q0 - Qv);
-      const float Mxx = -(gx * gx * Q0 - 2.f * gx * Qu + Quu);
-      const float Mxy = -(gx * gy * Q0 - gx * Qv - gy * Qu + Quv);
-      const float Myy = -(gy * gy * Q0 - 2.f * gy * Qv + Qvv);
-      float* o = partials + P * TGS_PARTIAL_FLOATS;
-      st4(o, make_float4(A * Mx + B * My, B * Mx + Cc * My, s0.w, Q0 / a0.w));
-      st4(o + 4, make_float4(0.5f * Mxx, Mxy, 0.5f * Myy, s0.x));
-      st4(o + 8, make_float4(s0.y, s0.z, 0.f, 0.f));
+      // s1 = {Q0, Qu, Qv, Quu}, s2 = {Quv, Qvv, -, -}
+      store_partial(partials, P, a0.x, a0.y, a1.x, a1.y, a1.z, a0.w, s1.x, s1.y, s1.z, s1.w, s2.y, s2.x, s0);
     }
   }
 }
@@ -1848,8 +1650,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TGS_QUAD_WA
   __shared__ int s_clamp[2], s_stager[2], s_arrive;
   __shared__ float4 recs2[2 * 64 * 3];  // two batches of staged records: the next one is staged while this one is walked
   __shared__ float4 sums[4 * 64 * 4];   // [quadrant][Gaussian j][16 slots]
-  constexpr int RED_RS = 68;
-  constexpr int RED_ROWS = 8;
   __shared__ float4 red4[4 * RED_ROWS * RED_RS / 4];
   // A resident grid takes the schedule's slots (block b of the one-wave kernel = entry b of tile_order) as workgroups
   // become free: slot 8 i + x belongs to XCD x, whose workgroups draw i from the XCD's counter (zeroed by k_raster_bwd,
@@ -1893,35 +1693,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TGS_QUAD_WA
   if (inb) {
     const float Tf = final_T[p];
     T = Tf;
-    float vA = v_alpha ? v_alpha[p] : 0.f;
-    if (v_rgb) { vCr = v_rgb[3 * p]; vCg = v_rgb[3 * p + 1]; vCb = v_rgb[3 * p + 2]; }
-    if (v_depth) vD = v_depth[p];
-    if (loss.on) {
-      if (loss.gt_rgb) {
-        const float d0 = out_rgb[3 * p] - loss.gt_rgb[3 * p];
-        const float d1 = out_rgb[3 * p + 1] - loss.gt_rgb[3 * p + 1];
-        const float d2 = out_rgb[3 * p + 2] - loss.gt_rgb[3 * p + 2];
-        vCr += loss.l1w * ((d0 > 0.f) - (d0 < 0.f));
-        vCg += loss.l1w * ((d1 > 0.f) - (d1 < 0.f));
-        vCb += loss.l1w * ((d2 > 0.f) - (d2 < 0.f));
-      }
-      if (loss.gt_depth) {
-        const float gd = loss.gt_depth[p];
-        if (gd > 0.f) {
-          const float alpha = fmaxf(1.f - Tf, 1e-10f);
-          const float ia = 1.0f / alpha;
-          const float dhat = out_depth[p] * ia;
-          const float r = dhat - gd;
-          float wgt = loss.dw;
-          if (loss.unc) wgt = wgt / (loss.uw * loss.unc[p] + loss.eps);
-          const float gdh = 2.f * wgt * r;
-          vD += gdh * ia;
-          if (1.f - Tf > 1e-10f) vA += -gdh * dhat * ia;
-        }
-      }
-    }
-    const float bgdot = cam.bg[0] * vCr + cam.bg[1] * vCg + cam.bg[2] * vCb;
-    SX = -Tf * (vA - bgdot);
+    float no_sum = 0.f;   // (the tile's loss sums are k_raster_bwd's)
+    const PixUpstream u = pixel_upstream<false>(loss, p, Tf, out_rgb, out_depth, v_rgb, v_depth, v_alpha, no_sum, no_sum);
+    vCr = u.vCr; vCg = u.vCg; vCb = u.vCb; vD = u.vD;
+    SX = -Tf * (u.vA - bg_dot_gr(cam, u));
   }
   // pixel constants of the quadrant (the operands eval_s takes for slot k)
   const PixConst pc = make_pix_const(lane);
@@ -1931,15 +1706,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TGS_QUAD_WA
   const float q5 = (k & 1) ? 1.f : 0.f, q6 = (k >> 1) ? 1.f : 0.f;   // Sx / Sy rows: the quadrant's 8-pixel offset
 
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int i = start + tmax + tid; i < end; i += 256) {   // behind the last stop position nothing received a gradient
-    const int gid = sorted_gid[i];
-    const size_t P = pair_index(group_base, gid, ld4(splats + (size_t)gid * TGS_SPLAT_FLOATS + 8), tx, ty);
-    float* o = partials + P * TGS_PARTIAL_FLOATS;
-    st4(o, z4); st4(o + 4, z4); st4(o + 8, z4);
-  }
+  zero_partials_behind(partials, group_base, splats, sorted_gid, tx, ty, start + tmax + tid, end, 256);
 
   float* red = reinterpret_cast<float*>(red4) + k * (RED_ROWS * RED_RS);
   float4* sums_k = sums + k * (64 * 4);
+  // make_red_table's table and, in the walk, reduce_round's round, written out: through the helpers this kernel's
+  // register allocation comes out differently (profiles/k7_shared_isa.txt); keep the two in step with the helpers
   const int red_c = lane & 15;
   const int red_part = (lane >> 4) ^ ((red_c >= 4 && red_c < 12) ? 1 : 0);
   float wt[16];
@@ -2084,18 +1856,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TGS_QUAD_WA
         s2.x += t2.x; s2.y += t2.y; s2.z += t2.z; s2.w += t2.w;
         s3.x += t3.x; s3.y += t3.y; s3.z += t3.z; s3.w += t3.w;
       }
-      const float4 a0 = cur.a0, a1 = cur.a1;
-      const float gx = a0.x, gy = a0.y;           // centre relative to the tile centre (set while staging)
-      const float A = a1.x, B = a1.y, Cc = a1.z;
-      const float Q0 = s1.x, Qu = s1.y + s1.z, Qv = s1.w + s2.x, Quu = s2.y + s2.z, Qvv = s2.w + s3.x, Quv = s3.y;
-      const float Mx = -(gx * Q0 - Qu), My = -(gy * Q0 - Qv);
-      const float Mxx = -(gx * gx * Q0 - 2.f * gx * Qu + Quu);
-      const float Mxy = -(gx * gy * Q0 - gx * Qv - gy * Qu + Quv);
-      const float Myy = -(gy * gy * Q0 - 2.f * gy * Qv + Qvv);
-      float* o = partials + cur.P * TGS_PARTIAL_FLOATS;
-      st4(o, make_float4(A * Mx + B * My, B * Mx + Cc * My, s0.w, Q0 / a0.w));
-      st4(o + 4, make_float4(0.5f * Mxx, Mxy, 0.5f * Myy, s0.x));
-      st4(o + 8, make_float4(s0.y, s0.z, 0.f, 0.f));
+      store_partial(partials, cur.P, cur.a0, cur.a1, s0, s1, s2, s3);
       }
     }
     cur = nxt;                                // (meaningful in the wave that staged the next batch: the only one that will use it)
@@ -2216,37 +1977,10 @@ __global__ __launch_bounds__(1024) void k_raster_bwd_scan(
       const float Tf = final_T[pi];
       T = Tf;
       lim[k] = min(stop_pos[pi], n);
-      float vA = v_alpha ? v_alpha[pi] : 0.f;
-      float vCr = 0.f, vCg = 0.f, vCb = 0.f, vD = 0.f;
-      if (v_rgb) { vCr = v_rgb[3 * pi]; vCg = v_rgb[3 * pi + 1]; vCb = v_rgb[3 * pi + 2]; }
-      if (v_depth) vD = v_depth[pi];
-      if (loss.on) {
-        if (loss.gt_rgb) {
-          const float d0 = out_rgb[3 * pi] - loss.gt_rgb[3 * pi];
-          const float d1 = out_rgb[3 * pi + 1] - loss.gt_rgb[3 * pi + 1];
-          const float d2 = out_rgb[3 * pi + 2] - loss.gt_rgb[3 * pi + 2];
-          vCr += loss.l1w * ((d0 > 0.f) - (d0 < 0.f));
-          vCg += loss.l1w * ((d1 > 0.f) - (d1 < 0.f));
-          vCb += loss.l1w * ((d2 > 0.f) - (d2 < 0.f));
-        }
-        if (loss.gt_depth) {
-          const float gd = loss.gt_depth[pi];
-          if (gd > 0.f) {
-            const float alpha = fmaxf(1.f - Tf, 1e-10f);
-            const float ia = 1.0f / alpha;
-            const float dhat = out_depth[pi] * ia;
-            const float r = dhat - gd;
-            float wgt = loss.dw;
-            if (loss.unc) wgt = wgt / (loss.uw * loss.unc[pi] + loss.eps);
-            const float gdh = 2.f * wgt * r;
-            vD += gdh * ia;
-            if (1.f - Tf > 1e-10f) vA += -gdh * dhat * ia;
-          }
-        }
-      }
-      const float bgdot = cam.bg[0] * vCr + cam.bg[1] * vCg + cam.bg[2] * vCb;
-      SX = -Tf * (vA - bgdot);
-      vr[k] = vCr; vg[k] = vCg; vb[k] = vCb; vd[k] = vD;
+      float no_sum = 0.f;   // (the tile's loss sums are k_raster_bwd's)
+      const PixUpstream up = pixel_upstream<false>(loss, pi, Tf, out_rgb, out_depth, v_rgb, v_depth, v_alpha, no_sum, no_sum);
+      SX = -Tf * (up.vA - bg_dot_gr(cam, up));
+      vr[k] = up.vCr; vg[k] = up.vCg; vb[k] = up.vCb; vd[k] = up.vD;
     }
     Tm[k] = head ? T : 1.f;
     SXs[k] = head ? SX : 0.f;
@@ -2267,12 +2001,7 @@ __global__ __launch_bounds__(1024) void k_raster_bwd_scan(
   for (int i = 0; i < 16; i++) tmax = max(tmax, s_blim[i]);
   if (tmax <= quad.scan_min) return;                  // the four-wave launch's tile (same predicate there)
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int i = start + tmax + tid; i < end; i += 1024) {   // behind the last stop position nothing received a gradient
-    const int gid = sorted_gid[i];
-    const size_t P = pair_index(group_base, gid, ld4(splats + (size_t)gid * TGS_SPLAT_FLOATS + 8), tx, ty);
-    float* o = partials + P * TGS_PARTIAL_FLOATS;
-    st4(o, z4); st4(o + 4, z4); st4(o + 8, z4);
-  }
+  zero_partials_behind(partials, group_base, splats, sorted_gid, tx, ty, start + tmax + tid, end, 1024);
   const int blk = 4 * by + bx;
   const float u = (float)(4 * bx + row) - 7.5f, uu = u * u;
   const float vb0 = (float)(4 * by) - 7.5f;
@@ -2295,15 +2024,8 @@ __global__ __launch_bounds__(1024) void k_raster_bwd_scan(
     const float* t = tot + ((bi & 1) * 64 + lane) * SCAN_ENT;
     const float4 t0 = ld4(t), t1 = ld4(t + 4);
     const float2 t2 = *reinterpret_cast<const float2*>(t + 8);
-    const float Q0 = t1.x, Qu = t1.y, Qv = t1.z, Quu = t1.w, Quv = t2.x, Qvv = t2.y;
-    const float Mx = -(pgx * Q0 - Qu), My = -(pgy * Q0 - Qv);
-    const float Mxx = -(pgx * pgx * Q0 - 2.f * pgx * Qu + Quu);
-    const float Mxy = -(pgx * pgy * Q0 - pgx * Qv - pgy * Qu + Quv);
-    const float Myy = -(pgy * pgy * Q0 - 2.f * pgy * Qv + Qvv);
-    float* o = partials + pP * TGS_PARTIAL_FLOATS;
-    st4(o, make_float4(pA * Mx + pB * My, pB * Mx + pC * My, t0.w, Q0 / popac));
-    st4(o + 4, make_float4(0.5f * Mxx, Mxy, 0.5f * Myy, t0.x));
-    st4(o + 8, make_float4(t0.y, t0.z, 0.f, 0.f));
+    // t1 = {Q0, Qu, Qv, Quu}, t2 = {Quv, Qvv}
+    store_partial(partials, pP, pgx, pgy, pA, pB, pC, popac, t1.x, t1.y, t1.z, t1.w, t2.y, t2.x, t0);
   };
 
   for (int bi = 0; bi < nb; bi++) {
