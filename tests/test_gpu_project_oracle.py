@@ -335,6 +335,24 @@ def test_k8_partials_form(dev, name):
     _check_k8(case, "partials", got, vxy.cpu().double().numpy(), S, A, v32[:, :10], rad.cpu().numpy())
 
 
+def test_k8_forms_agree(dev):
+    """The two K8 kernels share one B.5 body (sh_color_bwd) and one geom_bwd and are compiled with fusion decided per
+    source expression, so they give the same bits: on the last 257 rows of all strata together (two workgroups, the
+    second with a single row) the partials form (k_project_bwd_lds: storage is 16 bases) equals the v_splats form
+    (k_project_bwd) fed K8a's sum of the same records, in every output."""
+    from touch_gs_amd import ops
+    tog = CASES["together"]
+    case = tog.take(np.arange(tog.N - 257, tog.N), name="together")
+    assert case.Ks == 16 and case.P["sh"] is not None
+    D, cam, sp, rad, gb, buf, S, A, hits, v32 = _k8_partials(case, dev)
+    args = (cam, D["means"], D["log_scales"], D["quats"], D["opac_logit"], D["sh"], case.deg, sp)
+    lds = ops.project_bwd(*args, group_base=gb, partials=buf, want_v_xy=True)
+    gen = ops.project_bwd(*args, v_splats=ops.reduce_partials(cam, sp, gb, buf), want_v_xy=True)
+    for k, a, b in zip(PARAM_KEYS + ("v_xy",), lds, gen):
+        assert not torch.isnan(a).any(), k
+        assert torch.equal(a, b), (k, int((a != b).sum()))
+
+
 @pytest.mark.parametrize("rows", [None, 256])
 def test_k8_colour_form(dev, rows):
     """tgs_project_bwd_color on all strata together, whole and for rows (256, N): the geometry gradients meet the same

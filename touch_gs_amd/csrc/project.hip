@@ -7,6 +7,20 @@
 //
 // Roofline: pure streaming, HBM bound.  Forward reads 44+12K B and writes 48 B per Gaussian;
 // backward reads 44+12K+48 (+48*tiles_hit of partials) and writes 44+12K (+8) B per Gaussian.
+//
+// Shared by the kernels of this file, each written once (the kernels differ in where the SH rows live and in what
+// follows the gradients):
+//   sh_basis, sh_color                the forward colour: K1 and the colour prefetch of the optimizer kernels
+//   load_gaussian, load_scale_quat    a Gaussian's parameters into registers: K1, K8 and the optimizer kernels
+//   geom_eval, project_fwd_core       K1 after the loads: the stand-alone kernels and every front prefetch
+//   group_sum_partials (K8a)          k_reduce_partials and both K8 kernels
+//   sh_color_bwd, geom_bwd            B.5 and B.8 backward: k_project_bwd and k_project_bwd_lds, which must agree
+//   sh_grad_row_store                 the SH gradient row in global memory: k_project_bwd and k_sh_op
+//   color_block_trailer / _flag_overflow, store_geom_grads     what both K8 kernels write besides the SH gradient
+//   ShImage, sh_image_load / _store, sh_image_bytes, adam_sh_stream, adam_geom, param_segs    tgs_adam.h
+// Left written out: the direction of sh_color (an fmaf chain) against that of sh_color_bwd (a plain expression) -- the
+// two round differently and both roundings are pinned; each K8 kernel's way of filling the coefficient registers and of
+// writing the SH gradient; the eight front-buffer pointers of the kernels that run K1, one __restrict__ parameter each.
 #include "tgs_adam.h"
 #include "tgs_binning.h"
 #include <cstddef>
@@ -248,6 +262,20 @@ __device__ __forceinline__ void geom_eval(const CamK& cam, const float* m, const
   G.det = G.c00 * G.c11 - G.c01 * G.c01;
 }
 
+// The parameters of Gaussian g into registers: all of them (K1 and the optimizer kernels that run it), or log-scales and
+// quaternion alone for a kernel that already holds the mean (K8 reads them only where geom_bwd or Adam follows).
+__device__ __forceinline__ void load_scale_quat(const float* log_scales, const float* quats, int g, float* ls, float* q) {
+  ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
+  const float4 q4 = ld4(quats + 4 * (size_t)g);
+  q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+}
+__device__ __forceinline__ void load_gaussian(const float* means, const float* log_scales, const float* quats,
+                                              const float* opac_logit, int g, float* m, float* ls, float* q, float& ol) {
+  m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];
+  load_scale_quat(log_scales, quats, g, ls, q);
+  ol = opac_logit[g];
+}
+
 // ---------------------------------------------------------------------------------------------
 // K1 forward
 // ---------------------------------------------------------------------------------------------
@@ -350,11 +378,7 @@ __device__ __forceinline__ void project_fwd_body(
   float m[3] = {0.f, 0.f, 0.f}, ls[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f};
   float ol = 0.f;
   if (g < N) {
-    m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];
-    ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
-    const float4 q4 = ld4(quats + 4 * (size_t)g);
-    q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-    ol = opac_logit[g];
+    load_gaussian(means, log_scales, quats, opac_logit, g, m, ls, q, ol);
     if constexpr (DEG >= 0 && !PRE) {
       sh_color<DEG>(m, cam.campos, sh + (size_t)g * sh_stride * 3, rgb);
     } else if (colors_in) {
@@ -422,11 +446,7 @@ __global__ __launch_bounds__(256) void k_adam_geom_project_next(
   float m[3] = {0.f, 0.f, 0.f}, ls[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f};
   float ol = 0.f;
   if (g < N) {
-    m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];
-    ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
-    const float4 q4 = ld4(quats + 4 * (size_t)g);
-    q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-    ol = opac_logit[g];
+    load_gaussian(means, log_scales, quats, opac_logit, g, m, ls, q, ol);
     adam_geom_flat(ad, g, m, ls, q, ol, grads, means, log_scales, quats, opac_logit, exp_avg, exp_avg_sq);
     sh_color<DEG>(m, cam.campos, sh + (size_t)g * sh_stride * 3, rgb);
   }
@@ -698,6 +718,74 @@ __device__ __forceinline__ void geom_bwd(const CamK& cam, const float* m, const 
     for (int j = 0; j < 4; j++) vq[j] = (vqn[j] - G.qn[j] * dot) * iq;
 }
 
+// B.5 backward for one Gaussian: ck = its 3K coefficients in registers (basis k, channel ch at 3k + ch), v[7..9] the
+// upstream colour gradient.  -> Y (the basis at the view direction), vr (the clamp-gated colour gradient; the SH
+// gradient is the outer product Y (x) vr, which each caller writes its own way), and the gradient through the view
+// direction accumulated into vm.  The direction is a plain expression here and an fmaf chain in sh_color: the two round
+// differently and both roundings are pinned (tests/test_gpu_project_oracle.py), so they stay apart.
+template <int DEG>
+__device__ __forceinline__ void sh_color_bwd(const float* m, const float* campos, const float* ck, const float* v,
+                                             float* Y, float* vr, float* vm) {
+  constexpr int K = (DEG + 1) * (DEG + 1);
+  float dx = m[0] - campos[0], dy = m[1] - campos[1], dz = m[2] - campos[2];
+  const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
+  const float d[3] = {dx * inv, dy * inv, dz * inv};
+  sh_basis<DEG>(d[0], d[1], d[2], Y);
+  float col[3] = {0.5f, 0.5f, 0.5f};
+#pragma unroll
+  for (int k = 0; k < K; k++)
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) col[ch] += Y[k] * ck[3 * k + ch];
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) vr[ch] = (col[ch] > 0.f) ? v[7 + ch] : 0.f;  // clamp gate
+  if constexpr (DEG >= 1) {
+    float dY[K][3];
+    sh_basis_grad<DEG>(d[0], d[1], d[2], dY);
+    float vd[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 1; k < K; k++) {
+      const float s = ck[3 * k] * vr[0] + ck[3 * k + 1] * vr[1] + ck[3 * k + 2] * vr[2];
+      vd[0] += dY[k][0] * s; vd[1] += dY[k][1] * s; vd[2] += dY[k][2] * s;
+    }
+    const float dot = d[0] * vd[0] + d[1] * vd[1] + d[2] * vd[2];
+#pragma unroll
+    for (int j = 0; j < 3; j++) vm[j] += (vd[j] - d[j] * dot) * inv;
+  }
+}
+
+// One Gaussian's SH gradient row Y (x) vr in global memory: K active bases, zeros up to the stored sh_stride.
+template <int DEG>
+__device__ __forceinline__ void sh_grad_row_store(float* o, int sh_stride, const float* Y, const float* vr) {
+  constexpr int K = (DEG + 1) * (DEG + 1);
+#pragma unroll
+  for (int k = 0; k < K; k++) { o[3 * k] = Y[k] * vr[0]; o[3 * k + 1] = Y[k] * vr[1]; o[3 * k + 2] = Y[k] * vr[2]; }
+  for (int k = K; k < sh_stride; k++) { o[3 * k] = 0.f; o[3 * k + 1] = 0.f; o[3 * k + 2] = 0.f; }
+}
+
+// The tail of a rank's colour-gradient block v_color[N,3] | campos[3] | flag (data-parallel step; read by
+// sh_grad_gathered and k_dp_agree_overflow): this view's camera position and a clear flag, or -- from a frame whose
+// binning overflowed, which writes nothing else -- the raised flag that tells the other ranks.
+__device__ __forceinline__ void color_block_trailer(float* v_color, int N, const float* campos) {
+  v_color[3 * (size_t)N] = campos[0]; v_color[3 * (size_t)N + 1] = campos[1];
+  v_color[3 * (size_t)N + 2] = campos[2]; v_color[3 * (size_t)N + 3] = 0.f;
+}
+__device__ __forceinline__ void color_block_flag_overflow(float* v_color, int N) { v_color[3 * (size_t)N + 3] = 1.f; }
+
+// What K8 writes per Gaussian besides its SH / colour gradient: the echo of the screen-space gradient (if wanted) and,
+// GRADS, the gradients of the 11 geometry parameters (not GRADS: the fused kernel hands them to Adam instead).
+template <bool GRADS>
+__device__ __forceinline__ void store_geom_grads(int g, const float* v, const float* vm, const float* vls, const float* vq,
+                                                 float vol, float* v_xy, float* v_means, float* v_log_scales,
+                                                 float* v_quats, float* v_opac_logit) {
+  if (v_xy) { v_xy[2 * g] = v[0]; v_xy[2 * g + 1] = v[1]; }
+  if constexpr (GRADS) {
+    v_means[3 * g] = vm[0]; v_means[3 * g + 1] = vm[1]; v_means[3 * g + 2] = vm[2];
+    v_log_scales[3 * g] = vls[0]; v_log_scales[3 * g + 1] = vls[1]; v_log_scales[3 * g + 2] = vls[2];
+    st4(v_quats + 4 * (size_t)g, make_float4(vq[0], vq[1], vq[2], vq[3]));
+    v_opac_logit[g] = vol;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // K8 backward
 // ---------------------------------------------------------------------------------------------
@@ -714,13 +802,10 @@ __global__ __launch_bounds__(256) void k_project_bwd(
   __shared__ RunScan S;
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (guard && guard[1]) {  // overflowed frame: the pair index space is not backed by memory
-    if (v_color && g == 0) v_color[3 * (size_t)N + 3] = 1.f;   // tell the other ranks (tgs_dp_agree_overflow)
+    if (v_color && g == 0) color_block_flag_overflow(v_color, N);
     return;
   }
-  if (v_color && g == 0) {  // trailer of the colour-gradient block: this view's camera position
-    v_color[3 * (size_t)N] = cam.campos[0]; v_color[3 * (size_t)N + 1] = cam.campos[1];
-    v_color[3 * (size_t)N + 2] = cam.campos[2]; v_color[3 * (size_t)N + 3] = 0.f;
-  }
+  if (v_color && g == 0) color_block_trailer(v_color, N, cam.campos);
   // per-Gaussian upstream gradient: {v_x, v_y, v_depth, v_opac, v_a, v_b, v_c, v_r, v_g, v_b}
   float v[10];
   if (partials) group_sum_partials(splats, group_base, partials, g, N, v, S, cam.long_run);   // (workgroup-uniform: every thread calls)
@@ -734,50 +819,18 @@ __global__ __launch_bounds__(256) void k_project_bwd(
   }
   const float m[3] = {means[3 * g], means[3 * g + 1], means[3 * g + 2]};
   float vm[3] = {0.f, 0.f, 0.f};
+  const float vol = v[3] * sigmoid_deriv(opac_logit[g]);
 
-  v_opac_logit[g] = v[3] * sigmoid_deriv(opac_logit[g]);
-
-  // ---- SH colour backward (B.5) ----
+  // ---- SH colour backward (B.5), coefficients from / gradients to the Gaussian's row in global memory ----
   if constexpr (DEG >= 0) {
     constexpr int K = (DEG + 1) * (DEG + 1);
-    float dx = m[0] - cam.campos[0], dy = m[1] - cam.campos[1], dz = m[2] - cam.campos[2];
-    const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-    const float d[3] = {dx * inv, dy * inv, dz * inv};
-    float Y[16];
-    sh_basis<DEG>(d[0], d[1], d[2], Y);
     const float* c = sh + (size_t)g * sh_stride * 3;
-    float col[3] = {0.5f, 0.5f, 0.5f};
-    float ck[K][3];
+    float ck[3 * K], Y[16], vr[3];
 #pragma unroll
-    for (int k = 0; k < K; k++) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) { ck[k][ch] = c[3 * k + ch]; col[ch] += Y[k] * ck[k][ch]; }
-    }
-    float vr[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) vr[ch] = (col[ch] > 0.f) ? v[7 + ch] : 0.f;  // clamp gate
+    for (int i = 0; i < 3 * K; i++) ck[i] = c[i];
+    sh_color_bwd<DEG>(m, cam.campos, ck, v, Y, vr, vm);
     if (v_color) { v_color[3 * g] = vr[0]; v_color[3 * g + 1] = vr[1]; v_color[3 * g + 2] = vr[2]; }
-    if (v_sh) {
-      float* o_sh = v_sh + (size_t)g * sh_stride * 3;
-#pragma unroll
-      for (int k = 0; k < K; k++) {
-        o_sh[3 * k] = Y[k] * vr[0]; o_sh[3 * k + 1] = Y[k] * vr[1]; o_sh[3 * k + 2] = Y[k] * vr[2];
-      }
-      for (int k = K; k < sh_stride; k++) { o_sh[3 * k] = 0.f; o_sh[3 * k + 1] = 0.f; o_sh[3 * k + 2] = 0.f; }
-    }
-    if constexpr (DEG >= 1) {
-      float dY[K][3];
-      sh_basis_grad<DEG>(d[0], d[1], d[2], dY);
-      float vd[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 1; k < K; k++) {
-        const float s = ck[k][0] * vr[0] + ck[k][1] * vr[1] + ck[k][2] * vr[2];
-        vd[0] += dY[k][0] * s; vd[1] += dY[k][1] * s; vd[2] += dY[k][2] * s;
-      }
-      const float dot = d[0] * vd[0] + d[1] * vd[1] + d[2] * vd[2];
-#pragma unroll
-      for (int j = 0; j < 3; j++) vm[j] += (vd[j] - d[j] * dot) * inv;
-    }
+    if (v_sh) sh_grad_row_store<DEG>(v_sh + (size_t)g * sh_stride * 3, sh_stride, Y, vr);
   } else {
     if (v_sh) {
       float* o_sh = v_sh + (size_t)g * sh_stride * 3;
@@ -792,17 +845,11 @@ __global__ __launch_bounds__(256) void k_project_bwd(
   // a Gaussian passed the App. B culls iff its conic was written (a > 0)
   const bool visible = splats[(size_t)g * TGS_SPLAT_FLOATS + 4] > 0.f;
   if (visible) {
-    const float ls[3] = {log_scales[3 * g], log_scales[3 * g + 1], log_scales[3 * g + 2]};
-    const float4 q4 = ld4(quats + 4 * (size_t)g);
-    const float q[4] = {q4.x, q4.y, q4.z, q4.w};
+    float ls[3], q[4];
+    load_scale_quat(log_scales, quats, g, ls, q);
     geom_bwd(cam, m, ls, q, v, vm, vls, vq);
   }
-  v_means[3 * g] = vm[0]; v_means[3 * g + 1] = vm[1]; v_means[3 * g + 2] = vm[2];
-  v_log_scales[3 * g] = vls[0]; v_log_scales[3 * g + 1] = vls[1]; v_log_scales[3 * g + 2] = vls[2];
-  st4(v_quats + 4 * (size_t)g, make_float4(vq[0], vq[1], vq[2], vq[3]));
-  if (v_xy) {
-    v_xy[2 * g] = v[0]; v_xy[2 * g + 1] = v[1];
-  }
+  store_geom_grads<true>(g, v, vm, vls, vq, vol, v_xy, v_means, v_log_scales, v_quats, v_opac_logit);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -833,99 +880,51 @@ __global__ __launch_bounds__(256) void k_project_bwd_lds(
   // (nor is the next view's colour prefetch produced: its tag word keeps its old value)
   if (ad_in.guard && ad_in.guard[1]) {
     // colour mode (v_sh is the rank's colour-gradient block): the pad slot carries the overflow flag
-    if (COLOR_ONLY && blockIdx.x == 0 && threadIdx.x == 0) v_sh[3 * (size_t)N + 3] = 1.f;
+    if (COLOR_ONLY && blockIdx.x == 0 && threadIdx.x == 0) color_block_flag_overflow(v_sh, N);
     return;
   }
   const AdamK ad = FUSE_ADAM ? adam_resolve(ad_in) : ad_in;
   constexpr int K = (DEG + 1) * (DEG + 1);   // active bases; sh_stride == KS here
   static_assert(KS >= K && (3 * KS) % 4 == 0, "storage must hold the active degree in whole float4s");
-  static_assert(256 * (3 * KS + 4) * sizeof(float) >= sizeof(GroupScan), "the group scan of the front prefetch reuses the SH image");
-  constexpr int ROW = 3 * KS, RS = ROW + 4, F4 = ROW / 4;
+  static_assert(sh_image_bytes(KS) >= sizeof(GroupScan), "the group scan of the front prefetch reuses the SH image");
+  static_assert(sh_image_bytes(KS) >= sizeof(RunScan), "the run scan reuses the SH image");
+  using Im = ShImage<KS>;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x;
-  const int g0 = blockIdx.x * 256;
-  const int g = g0 + tid;
-  const int nrows = min(256, N - g0);
-  const size_t blk = (size_t)g0 * ROW;
+  const Im im = sh_image<KS>(KS, blockIdx.x * 256, N);
+  const int g = im.g0 + tid;
 
   // per-Gaussian upstream gradient {v_x, v_y, v_depth, v_opac, v_a, v_b, v_c, v_r, v_g, v_b}: the segmented sum of the
   // group's partial records, long runs shared by the whole workgroup.  Its scratch aliases the (not yet loaded) SH image.
-  static_assert(256 * (3 * KS + 4) * sizeof(float) >= sizeof(RunScan), "the run scan reuses the SH image");
   float v[10];
   group_sum_partials(splats, group_base, partials, g, N, v, *reinterpret_cast<RunScan*>(lds4), cam.long_run);
-  {
-    const int nf = nrows * F4;
-    for (int f0 = tid; f0 < nf; f0 += 256 * 4) {
-      float4 t[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (f0 + 256 * u < nf) {
-          // fused: the row is read again by the Adam stream below, keep it cached; otherwise this is
-          // the only read of the step
-          const float* src = sh + blk + 4 * (size_t)(f0 + 256 * u);
-          t[u] = FUSE_ADAM ? ld4(src) : ld4_nt(src);
-        }
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int f = f0 + 256 * u;
-        if (f < nf) { const int row = f / F4, c4 = f - row * F4; st4(lds + row * RS + 4 * c4, t[u]); }
-      }
-    }
-  }
+  sh_image_load<FUSE_ADAM>(im, sh, lds, tid);   // fused: the Adam stream below reads the rows again
   __syncthreads();
 
   float vm[3] = {0.f, 0.f, 0.f}, vls[3] = {0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f};
   float m[3] = {0.f, 0.f, 0.f}, ls[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f};
   float ol = 0.f, vol = 0.f;
   if constexpr (COLOR_ONLY) {
-    if (g == 0) {  // trailer of the colour-gradient block: this view's camera position
-      v_sh[3 * (size_t)N] = cam.campos[0]; v_sh[3 * (size_t)N + 1] = cam.campos[1];
-      v_sh[3 * (size_t)N + 2] = cam.campos[2]; v_sh[3 * (size_t)N + 3] = 0.f;
-    }
+    if (g == 0) color_block_trailer(v_sh, N, cam.campos);
   }
   if (g < N) {
     m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];
     ol = opac_logit[g];
     vol = v[3] * sigmoid_deriv(ol);
     // ---- SH colour backward (B.5), coefficients from / gradients to the LDS row ----
-    float dx = m[0] - cam.campos[0], dy = m[1] - cam.campos[1], dz = m[2] - cam.campos[2];
-    const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
-    const float d[3] = {dx * inv, dy * inv, dz * inv};
-    float Y[16];
-    sh_basis<DEG>(d[0], d[1], d[2], Y);
-    float* row = lds + tid * RS;
-    float ck[ROW];
+    float* row = lds + tid * Im::RS;
+    float ck[Im::ROW], Y[16], vr[3];
 #pragma unroll
-    for (int i = 0; i < F4; i++) {
+    for (int i = 0; i < Im::F4; i++) {
       const float4 t = ld4(row + 4 * i);
       ck[4 * i] = t.x; ck[4 * i + 1] = t.y; ck[4 * i + 2] = t.z; ck[4 * i + 3] = t.w;
     }
-    float col[3] = {0.5f, 0.5f, 0.5f};
-#pragma unroll
-    for (int k = 0; k < K; k++)
-#pragma unroll
-      for (int ch = 0; ch < 3; ch++) col[ch] += Y[k] * ck[3 * k + ch];
-    float vr[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) vr[ch] = (col[ch] > 0.f) ? v[7 + ch] : 0.f;  // clamp gate
-    if constexpr (DEG >= 1) {
-      float dY[K][3];
-      sh_basis_grad<DEG>(d[0], d[1], d[2], dY);
-      float vd[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 1; k < K; k++) {
-        const float s = ck[3 * k] * vr[0] + ck[3 * k + 1] * vr[1] + ck[3 * k + 2] * vr[2];
-        vd[0] += dY[k][0] * s; vd[1] += dY[k][1] * s; vd[2] += dY[k][2] * s;
-      }
-      const float dot = d[0] * vd[0] + d[1] * vd[1] + d[2] * vd[2];
-#pragma unroll
-      for (int j = 0; j < 3; j++) vm[j] += (vd[j] - d[j] * dot) * inv;
-    }
+    sh_color_bwd<DEG>(m, cam.campos, ck, v, Y, vr, vm);
     if constexpr (COLOR_ONLY) { v_sh[3 * g] = vr[0]; v_sh[3 * g + 1] = vr[1]; v_sh[3 * g + 2] = vr[2]; }
     // own row <- SH gradient (only this thread ever touches this row before the barrier)
 #pragma unroll
-    for (int i = 0; i < (COLOR_ONLY ? 0 : F4); i++) {
+    for (int i = 0; i < (COLOR_ONLY ? 0 : Im::F4); i++) {
       float4 t;   // element e of the row belongs to basis e / 3, channel e % 3; inactive bases get 0
       t.x = (4 * i) / 3 < K ? Y[(4 * i) / 3] * vr[(4 * i) % 3] : 0.f;
       t.y = (4 * i + 1) / 3 < K ? Y[(4 * i + 1) / 3] * vr[(4 * i + 1) % 3] : 0.f;
@@ -933,45 +932,22 @@ __global__ __launch_bounds__(256) void k_project_bwd_lds(
       t.w = (4 * i + 3) / 3 < K ? Y[(4 * i + 3) / 3] * vr[(4 * i + 3) % 3] : 0.f;
       st4(row + 4 * i, t);
     }
-    // ---- geometry backward (B.8) ----
-    if (splats[(size_t)g * TGS_SPLAT_FLOATS + 4] > 0.f) {
-      ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
-      const float4 q4 = ld4(quats + 4 * (size_t)g);
-      q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-      geom_bwd(cam, m, ls, q, v, vm, vls, vq);
-    } else if (FUSE_ADAM) {
-      ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
-      const float4 q4 = ld4(quats + 4 * (size_t)g);
-      q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-    }
-    if (v_xy) { v_xy[2 * g] = v[0]; v_xy[2 * g + 1] = v[1]; }
-    if constexpr (!FUSE_ADAM) {
-      v_means[3 * g] = vm[0]; v_means[3 * g + 1] = vm[1]; v_means[3 * g + 2] = vm[2];
-      v_log_scales[3 * g] = vls[0]; v_log_scales[3 * g + 1] = vls[1]; v_log_scales[3 * g + 2] = vls[2];
-      st4(v_quats + 4 * (size_t)g, make_float4(vq[0], vq[1], vq[2], vq[3]));
-      v_opac_logit[g] = vol;
-    } else {
-      // Adam on the 11 non-SH parameters of this Gaussian; the colour prefetch below looks from the NEXT camera at the
-      // UPDATED mean, and the front prefetch projects the updated parameters
+    // ---- geometry backward (B.8): only of a Gaussian that passed the culls; Adam steps the others' parameters too ----
+    const bool visible = splats[(size_t)g * TGS_SPLAT_FLOATS + 4] > 0.f;
+    if (visible || FUSE_ADAM) load_scale_quat(log_scales, quats, g, ls, q);
+    if (visible) geom_bwd(cam, m, ls, q, v, vm, vls, vq);
+    store_geom_grads<!FUSE_ADAM>(g, v, vm, vls, vq, vol, v_xy, v_means, v_log_scales, v_quats, v_opac_logit);
+    // Adam on the 11 non-SH parameters of this Gaussian; the colour prefetch below looks from the NEXT camera at the
+    // UPDATED mean, and the front prefetch projects the updated parameters
+    if constexpr (FUSE_ADAM)
       adam_geom<true>(ad, g, m, ls, q, ol, vm, vls, vq, vol, means, log_scales, quats, opac_logit, exp_avg, exp_avg_sq);
-    }
   }
   if constexpr (COLOR_ONLY) return;
   __syncthreads();
   // coalesced stream of the block's SH gradient image: out as v_sh, or through the Adam update (with a colour
   // prefetch the updated coefficients replace the consumed gradient in the image)
-  if constexpr (!FUSE_ADAM) {
-    const int nf = nrows * F4;
-    for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
-#pragma unroll
-      for (int u = 0; u < 2; u++) {
-        const int f = f0 + 256 * u;
-        if (f < nf) { const int row = f / F4, c4 = f - row * F4; st4(v_sh + blk + 4 * (size_t)f, ld4(lds + row * RS + 4 * c4)); }
-      }
-    }
-  } else {
-    adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, blk, nrows, F4, RS, tid, nx.colors != nullptr);
-  }
+  if constexpr (!FUSE_ADAM) sh_image_store(im, lds, v_sh, tid);
+  else adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, im, tid, nx.colors != nullptr);
   if constexpr (FUSE_ADAM) {
     // Colour prefetch: the next step's K1 needs, of the 3K updated coefficients, only the colour they
     // give from the next camera -- evaluate it here, where the updated row is on chip, and K1 reads
@@ -980,7 +956,7 @@ __global__ __launch_bounds__(256) void k_project_bwd_lds(
       __syncthreads();
       float rgb[3] = {0.f, 0.f, 0.f};
       if (g < N) {
-        sh_color<DEG>(m, nx.campos, lds + tid * RS, rgb);
+        sh_color<DEG>(m, nx.campos, lds + tid * Im::RS, rgb);
         nx.colors[3 * g] = rgb[0]; nx.colors[3 * g + 1] = rgb[1]; nx.colors[3 * g + 2] = rgb[2];
       }
       if (nx.fr.splats) {
@@ -1054,19 +1030,16 @@ __global__ __launch_bounds__(256) void k_adam_sh_gathered(
   // rows [row0, N) of the model; the gathered blocks hold exactly these rows (N - row0 colour gradients each)
   if (ad_in.guard && ad_in.guard[1]) return;   // a rank's frame overflowed (tgs_dp_agree_overflow): no update
   const AdamK ad = adam_resolve(ad_in);
-  const int ROW = 3 * sh_stride, RS = ROW + 4, F4 = ROW / 4;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x;
-  const int g0 = row0 + blockIdx.x * 256;
-  const int g = g0 + tid;
-  const int nrows = min(256, N - g0);
-  const size_t blk = (size_t)g0 * ROW;
+  const ShImage<0> im = sh_image<0>(sh_stride, row0 + blockIdx.x * 256, N);
+  const int g = im.g0 + tid;
   if (g < N)
     sh_grad_gathered<DEG>(world, v_color_all, (size_t)(N - row0), g - row0, means[3 * g], means[3 * g + 1],
-                          means[3 * g + 2], lds + tid * RS, F4);
+                          means[3 * g + 2], lds + tid * im.RS, im.F4);
   __syncthreads();
-  adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, blk, nrows, F4, RS, tid, false);
+  adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, im, tid, false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1096,14 +1069,11 @@ __global__ __launch_bounds__(256) void k_adam_sh_geom_next(
     long long capacity, int32_t* __restrict__ sticky, int32_t* __restrict__ tag, int32_t tag_value) {
   if (ad_in.guard && ad_in.guard[1]) return;   // a rank's frame overflowed: no update, the tag keeps its old value
   const AdamK ad = adam_resolve(ad_in);
-  const int ROW = 3 * sh_stride, RS = ROW + 4, F4 = ROW / 4;
   extern __shared__ float4 lds4[];
   float* lds = reinterpret_cast<float*>(lds4);
   const int tid = threadIdx.x;
-  const int g0 = blockIdx.x * 256;
-  const int g = g0 + tid;
-  const int nrows = min(256, N - g0);
-  const size_t blk = (size_t)g0 * ROW;
+  const ShImage<0> im = sh_image<0>(sh_stride, blockIdx.x * 256, N);
+  const int g0 = im.g0, g = g0 + tid;
   int row0 = 0, rows_c = N;
   const float* v_color_all = ct.blk[0];
 #pragma unroll
@@ -1114,20 +1084,18 @@ __global__ __launch_bounds__(256) void k_adam_sh_geom_next(
   // ---- the SH gradient sum_r Y(dir_r) (x) v_color_r of this row, in rank order, into the LDS image ----
   if (g < N) {
     m[0] = means[3 * g]; m[1] = means[3 * g + 1]; m[2] = means[3 * g + 2];   // the means the forward pass used
-    sh_grad_gathered<DEG>(world, v_color_all, (size_t)rows_c, g - row0, m[0], m[1], m[2], lds + tid * RS, F4);
+    sh_grad_gathered<DEG>(world, v_color_all, (size_t)rows_c, g - row0, m[0], m[1], m[2], lds + tid * im.RS, im.F4);
   }
   __syncthreads();
   // ---- Adam over the block's SH rows; the updated coefficients replace the consumed gradient in the image ----
-  adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, blk, nrows, F4, RS, tid, true);
+  adam_sh_stream(ad, sh, exp_avg, exp_avg_sq, lds, im, tid, true);
   __syncthreads();
   // ---- Adam on the 11 geometry parameters, then the next camera's colour from the LDS row ----
   if (g < N) {
-    ls[0] = log_scales[3 * g]; ls[1] = log_scales[3 * g + 1]; ls[2] = log_scales[3 * g + 2];
-    const float4 q4 = ld4(quats + 4 * (size_t)g);
-    q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+    load_scale_quat(log_scales, quats, g, ls, q);
     ol = opac_logit[g];
     adam_geom_flat(ad, g, m, ls, q, ol, grads, means, log_scales, quats, opac_logit, exp_avg, exp_avg_sq);
-    sh_color<DEG>(m, cam.campos, lds + tid * RS, rgb);
+    sh_color<DEG>(m, cam.campos, lds + tid * im.RS, rgb);
   }
   __syncthreads();     // the group scan of K1 takes over the SH image
   project_fwd_core<true>(cam, N, g, m, ls, q, ol, rgb, splats, radii, group_base, tile_count, rank, status,
@@ -1157,11 +1125,8 @@ __global__ __launch_bounds__(256) void k_sh_op(int N, int sh_stride, const float
     for (int k = 0; k < K; k++) { r += Y[k] * c[3 * k]; gg += Y[k] * c[3 * k + 1]; b += Y[k] * c[3 * k + 2]; }
     out[3 * g] = r; out[3 * g + 1] = gg; out[3 * g + 2] = b;
   } else {
-    const float v0 = coeffs_or_vout[3 * g], v1 = coeffs_or_vout[3 * g + 1], v2 = coeffs_or_vout[3 * g + 2];
-    float* o = out + (size_t)g * sh_stride * 3;
-#pragma unroll
-    for (int k = 0; k < K; k++) { o[3 * k] = Y[k] * v0; o[3 * k + 1] = Y[k] * v1; o[3 * k + 2] = Y[k] * v2; }
-    for (int k = K; k < sh_stride; k++) { o[3 * k] = 0.f; o[3 * k + 1] = 0.f; o[3 * k + 2] = 0.f; }
+    const float vr[3] = {coeffs_or_vout[3 * g], coeffs_or_vout[3 * g + 1], coeffs_or_vout[3 * g + 2]};
+    sh_grad_row_store<DEG>(out + (size_t)g * sh_stride * 3, sh_stride, Y, vr);
   }
 }
 
@@ -1172,6 +1137,11 @@ inline bool lds_k8_ok(int sh_deg, int sh_stride) {
 #define DISPATCH_DEG(M, deg)                                                                     \
   do {                                                                                           \
     switch (deg) { case 0: M(0); break; case 1: M(1); break; case 2: M(2); break; default: M(3); break; } \
+  } while (0)
+#define DISPATCH_DEG_OR_NONE(M, deg)   /* deg < 0 (or anything else): the instantiation without SH */ \
+  do {                                                                                           \
+    switch (deg) { case 0: M(0); break; case 1: M(1); break; case 2: M(2); break; case 3: M(3); break; \
+                   default: M(-1); break; }                                                      \
   } while (0)
 #define DISPATCH_DEG_KS(M, deg, ks)                                                              \
   do {                                                                                           \
@@ -1208,13 +1178,7 @@ extern "C" int tgs_project_fwd(const TgsCamera* cam, int N, const float* means,
   hipLaunchKernelGGL((k_project_fwd<D, false>), grid, block, 0, s, k, N, means, log_scales, quats, \
                      opac_logit, sh, sh_stride, colors_in, splats, radii, (int32_t*)nullptr,       \
                      (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, 0ll, (int32_t*)nullptr)
-  switch (sh_deg) {
-    case 0: LAUNCH(0); break;
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    default: LAUNCH(-1); break;
-  }
+  DISPATCH_DEG_OR_NONE(LAUNCH, sh_deg);
 #undef LAUNCH
   TGS_CHECK_LAUNCH();
   return TGS_OK;
@@ -1256,7 +1220,7 @@ extern "C" int tgs_project_bwd(const TgsCamera* cam, int N, const float* means,
   if (partials && sh && v_sh && sh_deg >= 0 && lds_k8_ok(sh_deg, sh_stride)) {
     AdamK none{};
     none.guard = skip_if_overflow;
-    const size_t lds_bytes = 256 * (size_t)(3 * sh_stride + 4) * sizeof(float);
+    const size_t lds_bytes = sh_image_bytes(sh_stride);
 #define LAUNCH_LDS(D, KS)                                                                        \
   hipLaunchKernelGGL((k_project_bwd_lds<D, KS, false>), grid, block, lds_bytes, s, k, N,         \
                      const_cast<float*>(means), const_cast<float*>(log_scales),                  \
@@ -1272,16 +1236,18 @@ extern "C" int tgs_project_bwd(const TgsCamera* cam, int N, const float* means,
   hipLaunchKernelGGL(k_project_bwd<D>, grid, block, 0, s, k, N, means, log_scales, quats,        \
                      opac_logit, sh, sh_stride, splats, group_base, partials, v_splats, v_means, \
                      v_log_scales, v_quats, v_opac_logit, v_sh, (float*)nullptr, v_xy, skip_if_overflow)
-  switch (sh_deg) {
-    case 0: LAUNCH(0); break;
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 3: LAUNCH(3); break;
-    default: LAUNCH(-1); break;
-  }
+  DISPATCH_DEG_OR_NONE(LAUNCH, sh_deg);
 #undef LAUNCH
   TGS_CHECK_LAUNCH();
   return TGS_OK;
+}
+
+// The colour prefetch request for the view of camera kn (no front prefetch: fr stays empty).
+static NextView next_view(const CamK& kn, float* colors, int32_t* tag, int32_t tag_value) {
+  NextView nx{};
+  nx.campos[0] = kn.campos[0]; nx.campos[1] = kn.campos[1]; nx.campos[2] = kn.campos[2];
+  nx.colors = colors; nx.tag = tag; nx.tag_value = tag_value;
+  return nx;
 }
 
 static int project_bwd_adam_impl(const TgsCamera* cam, int N, int sh_stride, int sh_deg,
@@ -1297,19 +1263,15 @@ static int project_bwd_adam_impl(const TgsCamera* cam, int N, int sh_stride, int
   const CamK k = make_camk(cam);
   AdamK a = make_adamk(N, sh_stride, spec, 1.0f);
   a.guard = skip_if_overflow;
-  float* means = params;
-  float* log_scales = params + a.e_means;
-  float* quats = params + a.e_scales;
-  float* opac = params + a.e_quats;
-  float* sh = params + a.e_opac;
+  const ParamSegs p = param_segs(params, a);
   const dim3 grid((N + 255) / 256), block(256);
-  const size_t lds_bytes = 256 * (size_t)(3 * sh_stride + 4) * sizeof(float);
+  const size_t lds_bytes = sh_image_bytes(sh_stride);
   hipStream_t s = (hipStream_t)stream;
 #define LAUNCH_F(D, KS)                                                                          \
-  hipLaunchKernelGGL((k_project_bwd_lds<D, KS, true>), grid, block, lds_bytes, s, k, N, means,   \
-                     log_scales, quats, opac, sh, splats, group_base, partials, (float*)nullptr, \
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, v_xy, a,\
-                     exp_avg, exp_avg_sq, nx)
+  hipLaunchKernelGGL((k_project_bwd_lds<D, KS, true>), grid, block, lds_bytes, s, k, N, p.means, \
+                     p.log_scales, p.quats, p.opac, p.sh, splats, group_base, partials,          \
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,         \
+                     (float*)nullptr, v_xy, a, exp_avg, exp_avg_sq, nx)
   DISPATCH_DEG_KS(LAUNCH_F, sh_deg, sh_stride);
 #undef LAUNCH_F
   TGS_CHECK_LAUNCH();
@@ -1334,12 +1296,9 @@ extern "C" int tgs_project_bwd_adam_next(const TgsCamera* cam, int N, int sh_str
                                          int32_t* color_tag, int32_t tag_value, void* stream) {
   TGS_CHECK_ARG(camera_ok(next_cam), "bad next camera");
   TGS_CHECK_ARG(colors_next && color_tag, "null colour prefetch buffer");
-  const CamK kn = make_camk(next_cam);
-  NextView nx;
-  nx.campos[0] = kn.campos[0]; nx.campos[1] = kn.campos[1]; nx.campos[2] = kn.campos[2];
-  nx.colors = colors_next; nx.tag = color_tag; nx.tag_value = tag_value;
-  return project_bwd_adam_impl(cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
-                               group_base, partials, v_xy, skip_if_overflow, nx, stream);
+  return project_bwd_adam_impl(cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats, group_base,
+                               partials, v_xy, skip_if_overflow,
+                               next_view(make_camk(next_cam), colors_next, color_tag, tag_value), stream);
 }
 
 // What the three entry points that run the NEXT view's K1 inside an optimizer kernel share once they have checked their
@@ -1388,12 +1347,12 @@ extern "C" int tgs_project_bwd_adam_next_front(const TgsCamera* cam, int N, int 
   TGS_CHECK_ARG(splats_next && group_base_next && tile_cursor_next && scratch_next && status_next, "null front buffer");
   TGS_CHECK_ARG(capacity_next >= 0 && capacity_next < (1ll << 31), "bad capacity");
   if (N <= 0) return TGS_OK;
-  NextView nx;
+  NextFront fr;
   if (const int rc = next_front_begin(__func__, next_cam, splats_next, radii_next, group_base_next, tile_cursor_next,
                                       capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared,
-                                      (hipStream_t)stream, &nx.fr)) return rc;
-  nx.campos[0] = nx.fr.cam.campos[0]; nx.campos[1] = nx.fr.cam.campos[1]; nx.campos[2] = nx.fr.cam.campos[2];
-  nx.colors = colors_next; nx.tag = tag_word; nx.tag_value = tag_value;
+                                      (hipStream_t)stream, &fr)) return rc;
+  NextView nx = next_view(fr.cam, colors_next, tag_word, tag_value);
+  nx.fr = fr;
   return project_bwd_adam_impl(cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
                                group_base, partials, v_xy, skip_if_overflow, nx, stream);
 }
@@ -1421,15 +1380,12 @@ extern "C" int tgs_adam_geom_project_next(const TgsCamera* next_cam, int N, int 
                                       &fr)) return rc;
   AdamK a = make_adamk(N, sh_stride, spec, grad_scale);
   a.guard = skip_if_overflow;
-  float* means = params;
-  float* log_scales = params + a.e_means;
-  float* quats = params + a.e_scales;
-  float* opac = params + a.e_quats;
-  const float* sh = params + a.e_opac;
+  const ParamSegs p = param_segs(params, a);
   const dim3 grid((N + 255) / 256), block(256);
-#define LAUNCH_G(D)                                                                                          \
-  hipLaunchKernelGGL((k_adam_geom_project_next<D>), grid, block, 0, s, fr.cam, N, sh_stride, means, log_scales, \
-                     quats, opac, sh, grads, a, exp_avg, exp_avg_sq, NEXT_FRONT_ARGS(fr), tag_word, tag_value)
+#define LAUNCH_G(D)                                                                                            \
+  hipLaunchKernelGGL((k_adam_geom_project_next<D>), grid, block, 0, s, fr.cam, N, sh_stride, p.means, p.log_scales, \
+                     p.quats, p.opac, (const float*)p.sh, grads, a, exp_avg, exp_avg_sq, NEXT_FRONT_ARGS(fr), tag_word, \
+                     tag_value)
   DISPATCH_DEG(LAUNCH_G, sh_deg);
 #undef LAUNCH_G
   TGS_CHECK_LAUNCH();
@@ -1510,17 +1466,8 @@ static int project_bin_sort_impl(const TgsCamera* cam, int N, const float* means
   hipLaunchKernelGGL((k_project_fwd_colors<D>), grid, block, 0, s, k, N, means, log_scales, quats, \
                      opac_logit, sh, sh_stride, colors_in, splats, radii, group_base, tile_cursor,  \
                      sc.rank, status, (long long)capacity, sticky_overflow, color_tag, tag_expect)
-    if (colors_in && color_tag && sh_deg >= 0) {
-      DISPATCH_DEG(LAUNCH_PRE, sh_deg);
-    } else {
-      switch (sh_deg) {
-        case 0: LAUNCH(0); break;
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 3: LAUNCH(3); break;
-        default: LAUNCH(-1); break;
-      }
-    }
+    if (colors_in && color_tag && sh_deg >= 0) DISPATCH_DEG(LAUNCH_PRE, sh_deg);
+    else DISPATCH_DEG_OR_NONE(LAUNCH, sh_deg);
 #undef LAUNCH
 #undef LAUNCH_PRE
     TGS_CHECK_LAUNCH();
@@ -1608,7 +1555,7 @@ extern "C" int tgs_project_bwd_color(const TgsCamera* cam, int N, const float* m
   if (lds_k8_ok(sh_deg, sh_stride)) {
     AdamK none{};
     none.guard = skip_if_overflow;
-    const size_t lds_bytes = 256 * (size_t)(3 * sh_stride + 4) * sizeof(float);
+    const size_t lds_bytes = sh_image_bytes(sh_stride);
 #define LAUNCH_C(D, KS)                                                                          \
   hipLaunchKernelGGL((k_project_bwd_lds<D, KS, false, true>), grid, block, lds_bytes, s, k, N,   \
                      const_cast<float*>(means), const_cast<float*>(log_scales),                  \
@@ -1696,7 +1643,7 @@ extern "C" int tgs_adam_step_sh_gathered_rows(int world, int N, int row_begin, i
   AdamK a = make_adamk(N, sh_stride, spec, grad_scale);   // segment offsets of the WHOLE model
   a.guard = skip_if_overflow;
   const dim3 grid((row_end - row_begin + 255) / 256), block(256);
-  const size_t lds_bytes = 256 * (size_t)(3 * sh_stride + 4) * sizeof(float);
+  const size_t lds_bytes = sh_image_bytes(sh_stride);
   hipStream_t s = (hipStream_t)stream;
 #define LAUNCH_G(D)                                                                              \
   hipLaunchKernelGGL((k_adam_sh_gathered<D>), grid, block, lds_bytes, s, world, row_begin, row_end, sh_stride, \
@@ -1735,7 +1682,7 @@ extern "C" int tgs_adam_sh_gathered_geom_project_next(
   TGS_CHECK_ARG(splats_next && group_base_next && tile_cursor_next && scratch_next && status_next, "null front buffer");
   TGS_CHECK_ARG(sh_deg >= 0 && sh_deg <= 3 && sh_stride >= (sh_deg + 1) * (sh_deg + 1), "bad SH degree / stride");
   TGS_CHECK_ARG((3 * sh_stride) % 4 == 0, "SH row (3*sh_stride floats) must be a multiple of 16 bytes");
-  TGS_CHECK_ARG(256 * (size_t)(3 * sh_stride + 4) * sizeof(float) >= sizeof(GroupScan), "SH storage too small for the fused tail (needs >= 4 bases)");
+  TGS_CHECK_ARG(sh_image_bytes(sh_stride) >= sizeof(GroupScan), "SH storage too small for the fused tail (needs >= 4 bases)");
   TGS_CHECK_ARG(n_chunks >= 1 && n_chunks <= 8 && chunk_begin && chunk_blocks, "1 .. 8 row chunks");
   ChunkTable ct;
   ct.n = n_chunks;
@@ -1752,12 +1699,13 @@ extern "C" int tgs_adam_sh_gathered_geom_project_next(
                                       &fr)) return rc;
   AdamK a = make_adamk(N, sh_stride, spec, grad_scale);
   a.guard = skip_if_overflow;
+  const ParamSegs p = param_segs(params, a);
   const dim3 grid((N + 255) / 256), block(256);
-  const size_t lds_bytes = 256 * (size_t)(3 * sh_stride + 4) * sizeof(float);
+  const size_t lds_bytes = sh_image_bytes(sh_stride);
 #define LAUNCH_T(D)                                                                                            \
-  hipLaunchKernelGGL((k_adam_sh_geom_next<D>), grid, block, lds_bytes, s, fr.cam, world, N, sh_stride, params,   \
-                     params + a.e_means, params + a.e_scales, params + a.e_quats, params + a.e_opac, grads, ct, a, \
-                     exp_avg, exp_avg_sq, NEXT_FRONT_ARGS(fr), tag_word, tag_value)
+  hipLaunchKernelGGL((k_adam_sh_geom_next<D>), grid, block, lds_bytes, s, fr.cam, world, N, sh_stride, p.means,  \
+                     p.log_scales, p.quats, p.opac, p.sh, grads, ct, a, exp_avg, exp_avg_sq, NEXT_FRONT_ARGS(fr), \
+                     tag_word, tag_value)
   DISPATCH_DEG(LAUNCH_T, sh_deg);
 #undef LAUNCH_T
   TGS_CHECK_LAUNCH();

@@ -1,7 +1,9 @@
 // tgs_adam.h -- the Adam update (adam1) shared by K9 (optim.hip) and the optimizer kernels of project.hip, and the two
-// traversals those four kernels share: adam_sh_stream (SH rows through an LDS image) and adam_geom (the other 11).
+// traversals those four kernels share: adam_sh_stream (SH rows through an LDS image) and adam_geom (the other 11);
+// the LDS SH image itself (ShImage: geometry, coalesced load and store, sh_image_bytes) and the flat layout's segments.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include "tgs_common.h"
 
 struct AdamK {
@@ -39,7 +41,76 @@ static inline AdamK make_adamk(int N, int sh_stride, const TgsAdamSpec* spec, fl
   return a;
 }
 
+// The five segments of a flat parameter buffer (the moments and the all-reduced gradients have the same layout).
+struct ParamSegs { float *means, *log_scales, *quats, *opac, *sh; };
+static inline ParamSegs param_segs(float* params, const AdamK& a) {
+  return {params, params + a.e_means, params + a.e_scales, params + a.e_quats, params + a.e_opac};
+}
+
+// Dynamic LDS of a kernel that stages the SH rows of its 256 Gaussians (ShImage below): [256][3 * sh_stride + 4] floats.
+constexpr size_t sh_image_bytes(int sh_stride) { return 256 * (size_t)(3 * sh_stride + 4) * sizeof(float); }
+
 #ifdef __HIPCC__
+// The LDS SH image of a workgroup: the SH rows (ROW = 3 * bases floats = F4 float4s each) of the nrows <= 256
+// consecutive Gaussians from g0 on, which are one contiguous block of `sh` starting at element blk, held as
+// lds[row * RS + column]; the pad RS = ROW + 4 makes a thread's ds_read_b128 of its own row conflict-free.
+// KS > 0: the number of stored bases is a compile-time constant of the kernel; KS = 0: it is sh_stride.
+template <int KS>
+struct ShImage {
+  static constexpr int ROW = 3 * KS, RS = ROW + 4, F4 = ROW / 4;
+  int g0, nrows;
+  size_t blk;
+};
+template <>
+struct ShImage<0> {
+  int ROW, RS, F4;
+  int g0, nrows;
+  size_t blk;
+};
+template <int KS>
+__device__ __forceinline__ ShImage<KS> sh_image(int sh_stride, int g0, int N) {
+  ShImage<KS> im;
+  if constexpr (KS == 0) { im.ROW = 3 * sh_stride; im.RS = im.ROW + 4; im.F4 = im.ROW / 4; }
+  im.g0 = g0;
+  im.nrows = min(256, N - g0);
+  im.blk = (size_t)g0 * im.ROW;
+  return im;
+}
+
+// sh -> image, fully coalesced, 4 float4 columns per thread and round.  CACHED: the rows are read again (by the Adam
+// stream), keep them cached; otherwise this is the only read of the step.
+template <bool CACHED, int KS>
+__device__ __forceinline__ void sh_image_load(const ShImage<KS>& im, const float* sh, float* lds, int tid) {
+  const int nf = im.nrows * im.F4;
+  for (int f0 = tid; f0 < nf; f0 += 256 * 4) {
+    float4 t[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (f0 + 256 * u < nf) {
+        const float* src = sh + im.blk + 4 * (size_t)(f0 + 256 * u);
+        t[u] = CACHED ? ld4(src) : ld4_nt(src);
+      }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int f = f0 + 256 * u;
+      if (f < nf) { const int row = f / im.F4, c4 = f - row * im.F4; st4(lds + row * im.RS + 4 * c4, t[u]); }
+    }
+  }
+}
+
+// image -> the block's rows of `out` (the SH gradient), fully coalesced
+template <int KS>
+__device__ __forceinline__ void sh_image_store(const ShImage<KS>& im, const float* lds, float* out, int tid) {
+  const int nf = im.nrows * im.F4;
+  for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+      const int f = f0 + 256 * u;
+      if (f < nf) { const int row = f / im.F4, c4 = f - row * im.F4; st4(out + im.blk + 4 * (size_t)f, ld4(lds + row * im.RS + 4 * c4)); }
+    }
+  }
+}
+
 // Bias corrections and the scheduled position learning rate kept in device memory (a captured hipGraph of the step is replayed with the
 // current step's values): same IEEE division / square root as make_adamk does on the host.
 __device__ __forceinline__ AdamK adam_resolve(AdamK a) {
@@ -62,21 +133,21 @@ __device__ __forceinline__ void adam1(const AdamK& a, float lr, float& p, float 
   p -= (lr * (m * a.ibc1)) / denom;
 }
 
-// Adam on the SH rows of a workgroup's `nrows` consecutive Gaussians, whose gradients sit in the LDS image
-// lds[row * RS + column] (F4 float4 columns per row): the block [blk, blk + nrows * 4 F4) of sh and of both moments is
-// streamed fully coalesced, 2 float4 columns per thread and round so that 6 independent loads are in flight.
+// Adam on the SH rows of a workgroup's image, whose gradients sit in it: the block of sh and of both moments is streamed
+// fully coalesced, 2 float4 columns per thread and round so that 6 independent loads are in flight.
 // keep: the updated coefficients replace the consumed gradient in the image (for a colour evaluation that follows).
 // The ONE body of the fused K8+Adam kernel, k_adam_sh_gathered and k_adam_sh_geom_next (project.hip).
+template <int KS>
 __device__ __forceinline__ void adam_sh_stream(const AdamK& ad, float* sh, float* exp_avg, float* exp_avg_sq, float* lds,
-                                               size_t blk, int nrows, int F4, int RS, int tid, bool keep) {
-  const int nf = nrows * F4;
+                                               const ShImage<KS>& im, int tid, bool keep) {
+  const int nf = im.nrows * im.F4;
   for (int f0 = tid; f0 < nf; f0 += 256 * 2) {
     float4 P[2], M[2], V[2];
 #pragma unroll
     for (int u = 0; u < 2; u++) {
       const int f = f0 + 256 * u;
       if (f < nf) {
-        const size_t e = blk + 4 * (size_t)f;
+        const size_t e = im.blk + 4 * (size_t)f;
         P[u] = ld4_nt(sh + e); M[u] = ld4_nt(exp_avg + ad.e_opac + e); V[u] = ld4_nt(exp_avg_sq + ad.e_opac + e);
       }
     }
@@ -84,16 +155,16 @@ __device__ __forceinline__ void adam_sh_stream(const AdamK& ad, float* sh, float
     for (int u = 0; u < 2; u++) {
       const int f = f0 + 256 * u;
       if (f < nf) {
-        const int row = f / F4, c4 = f - row * F4;
-        const float4 G = ld4(lds + row * RS + 4 * c4);
-        const size_t e = blk + 4 * (size_t)f;
+        const int row = f / im.F4, c4 = f - row * im.F4;
+        const float4 G = ld4(lds + row * im.RS + 4 * c4);
+        const size_t e = im.blk + 4 * (size_t)f;
         const int c = 4 * c4;  // column of the first element inside the 3K-float row; DC = columns 0..2
         adam1(ad, c < 3 ? ad.lr_dc : ad.lr_rest, P[u].x, G.x, M[u].x, V[u].x);
         adam1(ad, c + 1 < 3 ? ad.lr_dc : ad.lr_rest, P[u].y, G.y, M[u].y, V[u].y);
         adam1(ad, c + 2 < 3 ? ad.lr_dc : ad.lr_rest, P[u].z, G.z, M[u].z, V[u].z);
         adam1(ad, ad.lr_rest, P[u].w, G.w, M[u].w, V[u].w);
         st4_nt(sh + e, P[u]); st4_nt(exp_avg + ad.e_opac + e, M[u]); st4_nt(exp_avg_sq + ad.e_opac + e, V[u]);
-        if (keep) st4(lds + row * RS + 4 * c4, P[u]);
+        if (keep) st4(lds + row * im.RS + 4 * c4, P[u]);
       }
     }
   }
