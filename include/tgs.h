@@ -750,6 +750,40 @@ int tgs_tsdf_extract_points(int nx, int ny, int nz, float vox, const float* S, c
                             float w_min, const int64_t* offsets, float* points, float* normals, float* colors /*may be NULL*/,
                             int64_t* edge_id /*may be NULL*/, void* stream);
 
+/* The TSDF grid's zero level set as a TRIANGLE MESH: marching tetrahedra on the Kuhn (Freudenthal) split of every grid cell
+ *     (an ADDITION within TGS_VERSION 320: two new calls, nothing earlier changes; csrc/tsdf.hip).  The
+ *     definition is tests/tsdf_mesh_ref.py (fp64 NumPy); TsdfVolume.extract_mesh_local is the caller.  Grid, state, VALID
+ *     (Wt >= w_min) and f = S / Wt as above; a voxel is INSIDE iff it is valid and f < 0 (f == 0 is outside).
+ * CELL a = (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1: the eight voxel centres a + d, d in {0,1}^3; ACTIVE iff all eight are
+ *      valid.  Six TETRAHEDRA per cell, one per permutation pi of (x, y, z) in the order xyz, xzy, yxz, yzx, zxy, zyx, with
+ *      the corners 000 -> e_pi1 -> e_pi1 + e_pi2 -> 111; their edges are the corner pairs u <= v componentwise.
+ * EDGE (a, e): from voxel a to a + offset(e), e = 0 ... 6: +x, +y, +z, +x+y, +y+z, +x+z, +x+y+z; key 7 a + e.  A VERTEX
+ *      exists on it iff both ends are valid, exactly one is inside and an active cell contains the edge.  Its attributes
+ *      are those of tgs_tsdf_extract_points with the edge's two ends a, b (one device function serves both):
+ *      t = f_a / (f_a - f_b);  point_m = centre_a[m] + t vox where the offset has a 1 in m, centre_a[m] elsewhere;
+ *      normal = normalize((1 - t) g(a) + t g(b)), exactly 0 if the length is 0 or not finite;  colour = (1 - t) C_a / Wt_a
+ *      + t C_b / Wt_b.
+ * FACES: per active cell and tetrahedron the 4-bit inside mask (bit q = corner q) selects 0, 1 or 2 triangles from a
+ *      16-entry table that depends on the mask and on the permutation's parity alone (the quad's diagonal included),
+ *      counter-clockwise seen from the outside (from larger f).  Degenerate triangles (a corner with f == 0: t = 0) are kept.
+ * ORDER: vertices in key order, faces in (cell, tetrahedron, table) order: functions of the grid alone.  The index of the
+ *      vertex on edge (a', e') is vert_offsets[a'] + popcount(vmask[a'] & ((1 << e') - 1)).
+ * tgs_tsdf_mesh_count (three launches, a lane per voxel): flags [V] u8 (scratch that tgs_tsdf_mesh_emit reads again: bit 0
+ *      valid, bit 1 inside), ntri [V] u8 = the triangles of cell a (0 ... 12; 0 where there is no such cell), vmask [V] u8 =
+ *      the 7-bit mask of the vertices voxel a owns.  A grid with a dimension of 1 has no cells: all zeros.
+ * tgs_tsdf_mesh_emit (one launch): vert_offsets, tri_offsets [V] int64 = the caller's exclusive prefix sums of
+ *      popcount(vmask) and ntri; points, normals, colors (may be NULL; needs C) [n_vertices,3] fp32, edge_key [n_vertices]
+ *      int64 (may be NULL), faces [n_triangles,3] int32.  flags and vmask must be those the count wrote for the same state
+ *      and w_min.  No atomics; no order between lanes reaches an output.
+ * Every argument is checked before any launch, as above.  Accuracy and equality against the reference:
+ * tests/test_gpu_tsdf_mesh.py. */
+int tgs_tsdf_mesh_count(int nx, int ny, int nz, float vox, const float* S, const float* Wt, float w_min, uint8_t* vmask,
+                        uint8_t* ntri, uint8_t* flags, void* stream);
+int tgs_tsdf_mesh_emit(int nx, int ny, int nz, float vox, const float* S, const float* Wt, const float* C /*may be NULL*/,
+                       float w_min, const uint8_t* flags, const uint8_t* vmask, const int64_t* vert_offsets,
+                       const int64_t* tri_offsets, float* points, float* normals, float* colors /*may be NULL*/,
+                       int64_t* edge_key /*may be NULL*/, int32_t* faces, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

@@ -125,6 +125,8 @@ SIGNATURES = {
     "tgs_tsdf_integrate": (C.c_int, [_I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, C.POINTER(TgsTsdfView), _P]),
     "tgs_tsdf_extract_count": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, C.c_float, _P, _P]),
     "tgs_tsdf_extract_points": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "tgs_tsdf_mesh_count": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, C.c_float, _P, _P, _P, _P]),
+    "tgs_tsdf_mesh_emit": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tgs_peer_alloc": (C.c_int, [C.c_size_t, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "tgs_peer_open": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]),
     "tgs_peer_close": (C.c_int, [_P]),

@@ -2,11 +2,12 @@
 
     python -m touch_gs_amd.export tsdf --run <run_dir> --output-dir <dir> [--resolution 256 | --voxel-size m]
         [--bounds touch | gaussians | x0 y0 z0 x1 y1 z1] [--depth median|expected] [--weight inverse_variance|uniform]
-        [--views train|all]
+        [--views train|all] [--mesh]
     python -m touch_gs_amd.export gaussians --run <run_dir> --output-dir <dir>
 
 ``tsdf`` renders the run's views, fuses their depth into a TSDF in HIP (touch_gs_amd.tsdf) and writes
-``surface.ply`` (points, outward normals, colours: the grid's zero crossings), ``tsdf.npz`` (TsdfVolume.save) and
+``surface.ply`` (points, outward normals, colours: the grid's zero crossings), ``tsdf.npz`` (TsdfVolume.save) and, with
+``--mesh``, ``mesh.ply`` (the same level set as a triangle mesh: marching tetrahedra in HIP), and
 ``export.json`` (grid, options, counts, seconds per stage and, for a capture with ``gt_depth/`` -- the analytic one --, the
 surface metrics against the points back-projected from it).  ``gaussians`` writes the INRIA-layout ``point_cloud.ply`` that
 splat viewers read.  Points, normals and Gaussians are in the CAPTURE's metric frame: the centring and the scale that the
@@ -21,7 +22,7 @@ import time
 
 import numpy as np
 
-from .tsdf import fuse_model, surface_metrics, write_ply, write_ply_table
+from .tsdf import fuse_model, mesh_stats, surface_metrics, write_ply, write_ply_table
 
 
 def load_run(run_dir: str, device="cuda"):
@@ -100,8 +101,9 @@ def gt_surface_points(root: str, max_points: int = 400000) -> np.ndarray:
 
 def export_tsdf(run_dir: str, output_dir: str, resolution: int = 256, voxel_size=None, bounds=None, depth: str = "median",
                 weight: str = "inverse_variance", views: str = "train", device="cuda", w_min: float = 0.5,
-                loaded=None) -> dict:
-    """-> what export.json holds.  ``loaded`` = a (model, cfg, scene) of :func:`load_run`, to spare the reload."""
+                loaded=None, mesh: bool = False) -> dict:
+    """-> what export.json holds.  ``loaded`` = a (model, cfg, scene) of :func:`load_run`, to spare the reload.  ``mesh``:
+    also write mesh.ply and add the ``mesh`` block (tsdf.mesh_stats in the capture's frame, and the seconds)."""
     import torch
     clock = time.perf_counter
     t0 = clock()
@@ -131,6 +133,15 @@ def export_tsdf(run_dir: str, output_dir: str, resolution: int = 256, voxel_size
                             points=int(len(pts))),
                 seconds=dict(load=round(t1 - t0, 3), render_and_fuse=round(t2 - t1, 3), extract=round(t3 - t2, 3),
                              write=round(t4 - t3, 3)))
+    if mesh:
+        t5 = clock()
+        m = vol.extract_mesh(w_min)
+        t6 = clock()
+        verts = to_capture_frame(m["vertices"], scene)
+        write_ply(os.path.join(output_dir, "mesh.ply"), verts, m["normals"], m["colors"], m["faces"])
+        t7 = clock()
+        info["mesh"] = dict(mesh_stats(verts, m["faces"]), seconds=dict(extract=round(t6 - t5, 3), write=round(t7 - t6, 3)))
+        t4 = clock()                                         # (the metrics' seconds below start after the mesh)
     if os.path.isdir(os.path.join(scene.root, "gt_depth")):
         gt = gt_surface_points(scene.root)
         if len(gt):
@@ -189,9 +200,11 @@ def main(argv=None):
     t.add_argument("--depth", choices=("median", "expected"), default="median")
     t.add_argument("--weight", choices=("inverse_variance", "uniform"), default="inverse_variance")
     t.add_argument("--views", choices=("train", "all"), default="train")
+    t.add_argument("--mesh", action="store_true", help="also write mesh.ply: the level set as a triangle mesh")
     a = ap.parse_args(argv)
     if a.what == "tsdf":
-        info = export_tsdf(a.run, a.output_dir, a.resolution, a.voxel_size, a.bounds, a.depth, a.weight, a.views, a.device)
+        info = export_tsdf(a.run, a.output_dir, a.resolution, a.voxel_size, a.bounds, a.depth, a.weight, a.views, a.device,
+                           mesh=a.mesh)
     else:
         info = export_gaussians(a.run, a.output_dir, a.device)
     print(json.dumps(info))

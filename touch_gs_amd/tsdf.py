@@ -1,10 +1,13 @@
 """Export of the learned surface: TSDF fusion of rendered depth into a voxel grid and the grid's zero crossings as an oriented,
 coloured point cloud (include/tgs.h: tgs_tsdf_integrate / tgs_tsdf_extract_count / tgs_tsdf_extract_points; csrc/tsdf.hip;
-DESIGN 5.1k), surface metrics against ground-truth points, and a binary PLY writer.
+DESIGN 5.1k) or as a triangle mesh (tgs_tsdf_mesh_count / tgs_tsdf_mesh_emit), surface metrics against
+ground-truth points, mesh statistics, and a binary PLY writer.
 
     vol = fuse_model(model, cams, (lo, hi), resolution=256)
     cloud = vol.extract_points()
     write_ply("surface.ply", cloud["points"], cloud["normals"], cloud["colors"])
+    mesh = vol.extract_mesh()
+    write_ply("mesh.ply", mesh["vertices"], mesh["normals"], mesh["colors"], mesh["faces"])
 
 Nothing here is on the training path: a run that never exports issues none of these launches.  The fusion and the extraction
 run in HIP on the volume's device (there is no CPU path); the metrics and the file formats are host code.
@@ -136,6 +139,55 @@ class TsdfVolume:
                     colors=None if loc["colors"] is None else loc["colors"].cpu().numpy(),
                     edge_id=loc["edge_id"].cpu().numpy())
 
+    def extract_mesh_local(self, w_min: float = 1e-6, want_colors: Optional[bool] = None):
+        """The zero level set as a triangle mesh (marching tetrahedra on the Kuhn split of every cell), device
+        tensors in GRID-LOCAL coordinates: dict(points [n,3], normals [n,3], colors [n,3] | None, edge_key [n] int64 = 7 voxel
+        + edge class, faces [F,3] int32, vmask [V] uint8, ntri [V] uint8).  Vertices in edge_key order, faces in (cell,
+        tetrahedron, table) order.  One host read (the two totals); no emit launch for an empty mesh."""
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        if not w_min > 0:
+            raise ValueError("w_min must be positive")
+        want_colors = self.C is not None if want_colors is None else want_colors
+        if want_colors and self.C is None:
+            raise ValueError("the volume holds no colour")
+        nx, ny, nz = self.dims
+        dev, V = self.device, self.num_voxels
+        vmask, ntri, flags = (torch.empty(V, dtype=torch.uint8, device=dev) for _ in range(3))
+        with torch.cuda.device(dev):
+            _lib.check(lib.tgs_tsdf_mesh_count(nx, ny, nz, C.c_float(self.voxel_size), _lib.ptr(self.S), _lib.ptr(self.Wt),
+                                               C.c_float(w_min), _lib.ptr(vmask), _lib.ptr(ntri), _lib.ptr(flags), self._stream()),
+                       "tgs_tsdf_mesh_count")
+            popcount = torch.tensor([bin(m).count("1") for m in range(256)], dtype=torch.int64, device=dev)
+            nvert = popcount[vmask.long()]
+            v_incl, t_incl = torch.cumsum(nvert, 0, dtype=torch.int64), torch.cumsum(ntri, 0, dtype=torch.int64)
+            vert_offsets, tri_offsets = (v_incl - nvert).contiguous(), (t_incl - ntri).contiguous()
+            n_v, n_f = (int(x) for x in torch.stack([v_incl[-1], t_incl[-1]]).tolist())
+            if n_v >= 2 ** 31:
+                raise ValueError(f"the mesh has {n_v} vertices: more than an int32 face index holds")
+            points = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+            normals = torch.empty(n_v, 3, dtype=torch.float32, device=dev)
+            colors = torch.empty(n_v, 3, dtype=torch.float32, device=dev) if want_colors else None
+            edge_key = torch.empty(n_v, dtype=torch.int64, device=dev)
+            faces = torch.empty(n_f, 3, dtype=torch.int32, device=dev)
+            if n_v:
+                _lib.check(lib.tgs_tsdf_mesh_emit(nx, ny, nz, C.c_float(self.voxel_size), _lib.ptr(self.S), _lib.ptr(self.Wt),
+                                                  _lib.ptr(self.C) if want_colors else None, C.c_float(w_min), _lib.ptr(flags),
+                                                  _lib.ptr(vmask), _lib.ptr(vert_offsets), _lib.ptr(tri_offsets), _lib.ptr(points),
+                                                  _lib.ptr(normals), _lib.ptr(colors), _lib.ptr(edge_key), _lib.ptr(faces),
+                                                  self._stream()), "tgs_tsdf_mesh_emit")
+        return dict(points=points, normals=normals, colors=colors, edge_key=edge_key, faces=faces, vmask=vmask, ntri=ntri)
+
+    def extract_mesh(self, w_min: float = 1e-6) -> dict:
+        """The mesh as host arrays: vertices [n,3] float64 in the WORLD (the origin added in fp64), normals [n,3] float32,
+        colors [n,3] float32 or None, faces [F,3] int32 (counter-clockwise seen from the outside), edge_key [n] int64."""
+        loc = self.extract_mesh_local(w_min)
+        return dict(vertices=loc["points"].cpu().numpy().astype(np.float64) + self.origin,
+                    normals=loc["normals"].cpu().numpy(),
+                    colors=None if loc["colors"] is None else loc["colors"].cpu().numpy(),
+                    faces=loc["faces"].cpu().numpy(), edge_key=loc["edge_key"].cpu().numpy())
+
     def save(self, path: str) -> None:
         np.savez_compressed(path, S=self.S.cpu().numpy(), Wt=self.Wt.cpu().numpy(),
                             C=np.zeros((0, 3), np.float32) if self.C is None else self.C.cpu().numpy(), origin=self.origin,
@@ -234,24 +286,33 @@ def surface_metrics(points, gt_points, tau: float) -> dict:
                 n_points=len(p), n_gt=len(g), tau=float(tau))
 
 
-def write_ply_table(path: str, names: Sequence[str], columns: Sequence[np.ndarray], comment: Optional[str] = None) -> None:
+def write_ply_table(path: str, names: Sequence[str], columns: Sequence[np.ndarray], comment: Optional[str] = None,
+                    faces=None) -> None:
     """A binary little-endian PLY with one ``vertex`` element: column i is property ``names[i]``, float32 -- or uchar where
-    the array is uint8."""
+    the array is uint8 -- and, with ``faces`` [F,3], a ``face`` element of int32 triangles."""
     n = len(columns[0])
     fields = [(name, "u1" if col.dtype == np.uint8 else "<f4") for name, col in zip(names, columns)]
     rec = np.empty(n, dtype=fields)
     for (name, _), col in zip(fields, columns):
         rec[name] = col
     head = ["ply", "format binary_little_endian 1.0"] + ([f"comment {comment}"] if comment else []) + [f"element vertex {n}"]
-    head += [f"property {'uchar' if t == 'u1' else 'float'} {name}" for name, t in fields] + ["end_header"]
+    head += [f"property {'uchar' if t == 'u1' else 'float'} {name}" for name, t in fields]
+    tail = b""
+    if faces is not None:
+        tri = np.asarray(faces).reshape(-1, 3)
+        frec = np.empty(len(tri), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        frec["n"], frec["v"] = 3, tri
+        head += [f"element face {len(tri)}", "property list uchar int vertex_indices"]
+        tail = frec.tobytes()
     with open(path, "wb") as f:
-        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(("\n".join(head + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+        f.write(tail)
 
 
-def write_ply(path: str, points, normals=None, colors=None) -> None:
-    """A point cloud as binary little-endian PLY: x y z [nx ny nz] [red green blue], floats and uchar colours
-    (``colors`` in [0, 1])."""
+def write_ply(path: str, points, normals=None, colors=None, faces=None) -> None:
+    """A point cloud -- with ``faces`` [F,3] a triangle mesh -- as binary little-endian PLY: x y z [nx ny nz] [red green blue],
+    floats and uchar colours (``colors`` in [0, 1]); faces as ``property list uchar int vertex_indices``."""
     p = np.asarray(points, dtype=np.float64)
     names, cols = ["x", "y", "z"], [p[:, 0], p[:, 1], p[:, 2]]
     if normals is not None:
@@ -262,4 +323,36 @@ def write_ply(path: str, points, normals=None, colors=None) -> None:
         c = np.clip(np.rint(np.asarray(colors, dtype=np.float64) * 255.0), 0, 255).astype(np.uint8)
         names += ["red", "green", "blue"]
         cols += [c[:, 0], c[:, 1], c[:, 2]]
-    write_ply_table(path, names, cols)
+    write_ply_table(path, names, cols, faces=faces)
+
+
+def mesh_stats(vertices, faces) -> dict:
+    """What a viewer cannot tell at a glance: n_vertices, n_faces, boundary_edges (undirected edges with one face),
+    nonmanifold_edges (more than two faces, or two that run along it in the same direction), components (of the vertices
+    that faces reference), area, volume (signed, outward faces positive; meaningful when the mesh is closed) and
+    degenerate_faces (zero area)."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    out = dict(n_vertices=int(len(v)), n_faces=int(len(f)), boundary_edges=0, nonmanifold_edges=0, components=0, area=0.0,
+               volume=0.0, degenerate_faces=0)
+    if len(f) == 0:
+        return out
+    a, b = np.concatenate([f[:, 0], f[:, 1], f[:, 2]]), np.concatenate([f[:, 1], f[:, 2], f[:, 0]])
+    code, inv = np.unique(np.minimum(a, b) * len(v) + np.maximum(a, b), return_inverse=True)
+    count = np.bincount(inv, minlength=len(code))
+    forward = np.bincount(inv, weights=(a < b), minlength=len(code))
+    out["boundary_edges"] = int((count == 1).sum())
+    out["nonmanifold_edges"] = int(((count > 2) | ((count == 2) & (forward != 1))).sum())
+    used = np.unique(f)
+    graph = coo_matrix((np.ones(len(code)), (code // len(v), code % len(v))), shape=(len(v), len(v)))
+    labels = connected_components(graph, directed=False)[1]
+    out["components"] = int(len(np.unique(labels[used])))
+    p = v[f] - v[used].mean(0)                                  # (centred: the volume's terms stay small far from the origin)
+    cr = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    dbl = np.linalg.norm(cr, axis=1)
+    out["area"] = float(dbl.sum() / 2.0)
+    out["volume"] = float((np.cross(p[:, 0], p[:, 1]) * p[:, 2]).sum() / 6.0)
+    out["degenerate_faces"] = int((dbl == 0).sum())
+    return out
