@@ -569,6 +569,13 @@ int tgs_ssim_fwd_bwd(int W, int H, const float* img, const float* gt, float weig
 int tgs_ssim_fwd_bwd_rows(int W, int H, const float* img, const float* gt, float weight,
                           float* block_partials, int n_partials, float* v_img, float* scratch,
                           int y0, int y1, int count_y0, int count_y1, void* stream);
+/* Developer switch (A/B runs, tests; an ADDITION within TGS_VERSION 320): which kernels a gradient call of the two above runs.
+ *     0 = two kernels with the adjoint planes in scratch; 1 = one pass on that kernel's own grid (54-column strips; scratch
+ *     is not touched, the workgroup sums differ from form 0 by summation order); 2 = one pass on the grid of form 0 (scratch
+ *     is not touched, block_partials bit-identical to form 0); 3 = the default: form 2 from 1920 x 1080 pixels on, form 0
+ *     below.  v_img is bit-identical in all of them.  Environment TGS_SSIM_FUSED (read once at first use), a negative
+ *     argument leaves the setting; returns the form in force.  PROCESS-WIDE, like tgs_set_raster_variant. */
+int tgs_set_ssim_form(int form);
 
 /* Scale-invariant monocular depth loss  L = weight * (1 - rho)  (an ADDITION within TGS_VERSION 320: no struct and no earlier
  *     signature changes; csrc/depthcorr.hip).  rho = the Pearson correlation, over the VALID pixels, of the expected depth

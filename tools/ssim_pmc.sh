@@ -3,7 +3,7 @@
 #   bash tools/ssim_pmc.sh <tag>  -> gpurun_out/<tag>_ssim_pmc.json
 TAG=${1:-r6}; export TMPDIR=/tmp; cd ${GRAFT_REPO_ROOT:-.}; mkdir -p gpurun_out
 i=0
-for fused in 0 1; do
+for fused in 0 2; do
 for set in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" \
            "SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY GRBM_GUI_ACTIVE SQ_WAIT_INST_LDS" \
            "FETCH_SIZE" "WRITE_SIZE" "SQ_LEVEL_WAVES SQ_ACCUM_PREV_HIRES SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS"; do
@@ -13,7 +13,7 @@ for set in "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE
 done
 done
 rm -rf /tmp/ssimks0 /tmp/ssimks1
-for fused in 0 1; do TGS_SSIM_FUSED=$fused rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ssimks$fused -- python tools/ssim_only.py > /dev/null 2>&1; done
+for fused in 0 2; do TGS_SSIM_FUSED=$fused rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ssimks$fused -- python tools/ssim_only.py > /dev/null 2>&1; done
 python - <<PY
 import csv, glob, collections, json, re
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -28,7 +28,7 @@ for d in glob.glob("/tmp/ssimpmc*"):
                     if k in r: acc[m.group(0)]["_" + k] = [float(r[k])]
 out = {k: {c: sum(v) / len(v) for c, v in cs.items()} for k, cs in acc.items()}
 dur = {}
-for fz in (0, 1):
+for fz in (0, 2):
     for f in glob.glob(f"/tmp/ssimks{fz}/*/*kernel_stats.csv"):
         for r in csv.DictReader(open(f)):
             m = re.search(r"k_ssim_\w+", r["Name"])

@@ -116,6 +116,7 @@ SIGNATURES = {
     "tgs_adam_step": (C.c_int, [_I, _I, _P, _P, _P, _P, C.POINTER(TgsAdamSpec), C.c_float, C.c_int64, C.c_int64, _P, _P]),
     "tgs_ssim_fwd_bwd": (C.c_int, [_I, _I, _P, _P, C.c_float, _P, _P, _P, _P]),
     "tgs_ssim_fwd_bwd_rows": (C.c_int, [_I, _I, _P, _P, C.c_float, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    "tgs_set_ssim_form": (C.c_int, [_I]),
     "tgs_depth_corr_fwd_bwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
     "tgs_depth_corr_local_fwd_bwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, _I, _I, _I, _I, C.c_float,
                                               _P, _P, _P, _P, _P, _P]),

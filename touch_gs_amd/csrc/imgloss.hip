@@ -14,7 +14,10 @@
 // outputs (2.6x read amplification, 48 KB of LDS per workgroup, 3 workgroups per CU, 39-44 % LDS
 // bank-conflict cycles; 77 + 80 us at 1080p).  Read amplification here: 74/64 horizontally,
 // (SEG+10)/SEG vertically.  Roofline: HBM (9 adjoint planes written, then read).
+// From 1080p on a gradient call runs k_ssim_fused instead (below): both filters in one pass over the same strips, the adjoint
+// values in a two-row LDS ring instead of HBM, every output bit-identical (ssim_impl).
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include "tgs_common.h"
 
@@ -318,44 +321,59 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 
 
 // ---------------------------------------------------------------------------------------------
-// One pass (round 5): forward + backward of a strip without the adjoint planes in HBM
+// One pass: forward + backward of a strip without the adjoint planes in HBM
 // ---------------------------------------------------------------------------------------------
 // k_ssim_fwd writes nine adjoint values per pixel (75 MB at 1080p) that k_ssim_bwd reads back with its own halo
 // (x 1.5): 351 MB of HBM traffic for 75 MB of compulsory bytes (img, gt in; v_img out), 10 % of the train step.
-// Here a workgroup owns SWO = 54 output columns x SEG rows and keeps everything between the two filters on chip:
-// its 192 threads = (64 adjoint columns [xo0 - 5, xo0 + 59)) x 3 channels.  Per block of 11 staged input rows
-//   phase 1  = k_ssim_fwd's loop verbatim on the strip shifted by the halo: horizontal moments from LDS, the last 11 rows
-//              in registers, SSIM map + the three adjoint values of (row r - 5, own column) -> LDS (zero outside the
-//              image: the backward filter's zero padding), 11 rows x 64 x 9 floats;
-//   phase 2  = k_ssim_bwd's loop verbatim, reading those rows from LDS instead of staging them from HBM: horizontal
-//              filter of the three adjoint maps (threads of the 54 inner columns), the last 11 rows in registers,
-//              v_img of row r - 10.
-// Same arithmetic in the same order per value: v_img is bit-identical to the two-kernel path (test_ssim_one_pass_equals_two_kernels).
-// NOT the default -- it is slower (see ssim_impl).  Costs: the forward part
-// runs on (64 / 54) x ((SEG + 10) / SEG) more pixels, img / gt are read with a 10-pixel halo ((74 / 54) x ((SEG + 20) / SEG));
-// LDS 45 KB per workgroup (3 per CU).  The map sum counts a pixel in the workgroup that owns its OUTPUT.
-constexpr int SWO = SW - 2 * HALO;
+// Here a workgroup owns SWO output columns x SEG rows and keeps everything between the two filters on chip.  Its 256
+// threads are (column, channel) pairs: the first 3 (SWO + 10) of them run phase 1 on the strip's adjoint columns
+// [x0 - 5, x0 + SWO + 5), the first 3 SWO run phase 2 on its output columns.  Per staged input row r (11 to a block):
+//   phase 1  = k_ssim_fwd's loop body verbatim: horizontal moments from LDS, the last 11 rows in registers, SSIM map +
+//              the three adjoint values of (row r - 5, own column) -> LDS (zero outside the image: the backward
+//              filter's zero padding);
+//   barrier
+//   phase 2  = k_ssim_bwd's loop body verbatim on that ONE adjoint row: horizontal filter of the three adjoint maps from
+//              LDS, the last 11 rows in registers, v_img of row r - 10.
+// The backward's vertical window lives in registers, so only the row in flight has to be in LDS: a ring of two rows
+// (phase 1 fills one while slower waves still read the other; one barrier per row) in place of the 11 rows x 64 x 9
+// floats of the first one-pass kernel -- 27 KB of LDS instead of 45, 4 waves per SIMD instead of 2.
+// Same arithmetic in the same order per value: v_img is bit-identical to the two-kernel path.  The map sum is too when
+// the strips lie on the two-kernel path's grid (SWO = 64, segments of seg_rows(nblk) rows from the forward launch's
+// first row): every map value is added by the thread index, in the row order and to the workgroup slot k_ssim_fwd
+// adds it in (a thread of phase 1 sums its adjoint column; the sums move 15 threads down through LDS before the
+// wave reduction).  Costs: phase 1 runs on (SWO + 10) / SWO x (SEG + 10) / SEG more pixels, img / gt are read with a
+// 10-pixel halo, and with SWO = 64 the fourth wave has 30 lanes of phase 1 and nothing of phase 2.
+constexpr int FT = 256;             // threads of the one-pass kernel
+constexpr int SWO_OWN = SW - 2 * HALO;   // TGS_SSIM_FUSED=1: 54-column strips on the kernel's own grid
 __host__ __device__ constexpr int fused_seg_rows(int nblk) { return RB * nblk - 4 * HALO; }
 
-__global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_ssim_fused(
+template <int SWO>
+__global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_ssim_fused(
     int W, int H, float weight, const float* __restrict__ img, const float* __restrict__ gt,
-    float* __restrict__ v_img, float* __restrict__ block_partials, int n_partials, int NBLK,
-    int y_lo, int y_hi, int c_lo, int c_hi) {
-  const int SEG = fused_seg_rows(NBLK);
-  constexpr int ROWF = RowBlock<3>::ROWF;
-  constexpr int ADJF = SW * 9;                       // floats per adjoint row: [column][channel][3 maps]
+    float* __restrict__ v_img, float* __restrict__ block_partials, int n_partials, int SEG,
+    int y_base, int y_lo, int y_hi, int c_lo, int c_hi) {
+  // segment by of the grid that starts at row y_base owns the output rows [ys, ye) it shares with [y_lo, y_hi)
+  constexpr int NCA = SWO + 2 * HALO;                // adjoint columns of a strip
+  constexpr int NT1 = 3 * NCA, NT2 = 3 * SWO;        // threads of phase 1 / phase 2
+  constexpr int ROWF = (NCA + 2 * HALO) * 3;         // floats per staged input row: one per thread
+  constexpr int ADJF = NCA * 9;                      // floats per adjoint row: [column][channel][3 maps]
+  constexpr int SB = 6;                              // rows per staging round: 6 + 6 loads in flight beside the two windows
+  static_assert(ROWF <= FT && NT1 <= FT && FT <= RB * ROWF, "one staged float, one adjoint (column, channel) per thread");
   __shared__ float sa[RB * ROWF], sb[RB * ROWF];
-  __shared__ float sadj[RB * ADJF];
-  __shared__ float red[NTH / TGS_WAVE];
+  __shared__ float sadj[2 * ADJF];
+  __shared__ float red[FT / TGS_WAVE];
   const int tid = threadIdx.x;
-  const int col = tid / 3, c = tid - col * 3;
-  const int xa0 = blockIdx.x * SWO - HALO;           // first adjoint column of the strip (thread column 0)
-  const int gx = xa0 + col;
-  const int ys = y_lo + blockIdx.y * SEG, ye = min(ys + SEG, y_hi);
-  const bool own_col = col >= HALO && col < SW - HALO;
-  // phase 2 reads the 11 adjoint columns col - 5 .. col + 5; the threads of the halo columns produce no output and
-  // read a clamped (in-row) window instead
-  const int cb = min(max(col - HALO, 0), SWO - 1);
+  const unsigned ut = tid;                           // index of a global access: uniform base + 32-bit lane offset
+  const int col = tid / 3;
+  const int x0 = blockIdx.x * SWO;                   // first output column
+  // phase 1: this thread's adjoint column is x0 - 5 + col; phase 2: its output column is x0 + col (bounds kept uniform)
+  const bool own_col = col >= HALO && col < HALO + SWO;
+  const bool adj_in = col >= HALO - x0 && col < W + HALO - x0;
+  const bool out_in = tid < NT2 && col < W - x0;
+  const int yseg = y_base + blockIdx.y * SEG;
+  const int ys = max(yseg, y_lo), ye = min(yseg + SEG, y_hi);
+  const int xf0 = (x0 - 2 * HALO) * 3;               // staging: thread tid brings float xf0 + tid of an interleaved image row
+  const bool stage_x = tid < ROWF && tid >= -xf0 && tid < W * 3 - xf0;
   float w[RB][5], w2[RB][3];
 #pragma unroll
   for (int p = 0; p < RB; p++) {
@@ -364,90 +382,108 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     w2[p][0] = 0.f; w2[p][1] = 0.f; w2[p][2] = 0.f;
   }
   float msum = 0.f;
-  for (int blk = 0; blk < NBLK; blk++) {
-    const int r0 = ys - 2 * HALO + blk * RB;         // first input row of this block; its output rows are r0 - 10 ..
-    if (r0 - 2 * HALO >= ye) break;                  // no output row left (uniform)
-    __syncthreads();                                 // previous block fully consumed (sa / sb and sadj)
-    RowBlock<3>::stage2(img, gt, sa, sb, W, H, xa0, r0, tid);
-    __syncthreads();
-    // ---- phase 1: moments -> SSIM map -> adjoint values of row r0 + p - 5 at column gx
+  for (int r0 = ys - 2 * HALO; r0 - 2 * HALO < ye; r0 += RB) {   // r0 = first input row of the block; its output rows are r0 - 10 ..
+    __syncthreads();                                 // previous block fully consumed (sa / sb, and sadj[0] by its last row)
+#pragma unroll 1
+    for (int j0 = 0; j0 < RB; j0 += SB) {
+      float va[SB], vb[SB];
 #pragma unroll
-    for (int p = 0; p < RB; p++) {
-      const float* ra = sa + p * ROWF + tid;
-      const float* rb = sb + p * ROWF + tid;
-      float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; k++) {
-        const float a = ra[3 * k], b = rb[3 * k];
-        const float ga = WK(k) * a, gb = WK(k) * b;
-        m1 += ga; m2 += gb;
-        e11 = fmaf(ga, a, e11); e22 = fmaf(gb, b, e22); e12 = fmaf(ga, b, e12);
-      }
-      w[p][0] = m1; w[p][1] = m2; w[p][2] = e11; w[p][3] = e22; w[p][4] = e12;
-      const int gy = r0 + p - HALO;                  // map / adjoint row
-      float A = 0.f, B = 0.f, C = 0.f;
-      if (gy >= ys - HALO && gy < ye + HALO && gy >= 0 && gy < H) {      // uniform
-        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < WIN; k++) {
-#pragma unroll
-          for (int q = 0; q < 5; q++) o[q] = fmaf(WK(k), w[(p + 1 + k) % RB][q], o[q]);
-        }
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float mu1 = o[0], mu2 = o[1];
-        const float s11 = o[2] - mu1 * mu1, s22 = o[3] - mu2 * mu2, s12 = o[4] - mu1 * mu2;
-        const float n1 = 2.f * mu1 * mu2 + C1, n2 = 2.f * s12 + C2;
-        const float d1 = mu1 * mu1 + mu2 * mu2 + C1, d2 = s11 + s22 + C2;
-        const float id1 = __builtin_amdgcn_rcpf(d1), id2 = __builtin_amdgcn_rcpf(d2);
-        const float m = n1 * n2 * id1 * id2;
-        if (gx >= 0 && gx < W) {
-          if (own_col && gy >= ys && gy < ye && gy >= c_lo && gy < c_hi) msum += m;
-          const float dm_ds12 = 2.f * n1 * id1 * id2;
-          const float dm_ds11 = -m * id2;
-          const float dm_dmu1 = 2.f * mu2 * n2 * id1 * id2 - m * 2.f * mu1 * id1;
-          A = dm_dmu1 - 2.f * mu1 * dm_ds11 - mu2 * dm_ds12;
-          B = dm_ds11;
-          C = dm_ds12;
+      for (int u = 0; u < SB; u++) {
+        const int gy = r0 + j0 + u;
+        va[u] = 0.f; vb[u] = 0.f;
+        if (j0 + u < RB && stage_x && gy >= 0 && gy < H) {
+          const ptrdiff_t o = (ptrdiff_t)gy * W * 3 + xf0;      // uniform
+          va[u] = (img + o)[ut]; vb[u] = (gt + o)[ut];
         }
       }
-      float* o3 = sadj + p * ADJF + tid * 3;
-      o3[0] = A; o3[1] = B; o3[2] = C;
+#pragma unroll
+      for (int u = 0; u < SB; u++)
+        if (j0 + u < RB && tid < ROWF) { sa[(j0 + u) * ROWF + tid] = va[u]; sb[(j0 + u) * ROWF + tid] = vb[u]; }
     }
     __syncthreads();
-    // ---- phase 2: filtered adjoint maps -> v_img of row r0 + p - 10
 #pragma unroll
     for (int p = 0; p < RB; p++) {
-      const float* r = sadj + p * ADJF + (cb * 3 + c) * 3;
-      float h0 = 0.f, h1 = 0.f, h2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; k++) {
-        h0 = fmaf(WK(k), r[9 * k], h0);
-        h1 = fmaf(WK(k), r[9 * k + 1], h1);
-        h2 = fmaf(WK(k), r[9 * k + 2], h2);
-      }
-      w2[p][0] = h0; w2[p][1] = h1; w2[p][2] = h2;
-      const int gy = r0 + p - 2 * HALO;              // output row
-      if (gy >= ys && gy < ye) {                     // uniform
-        float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+      const int gyo = r0 + p - 2 * HALO;              // phase 2: output row
+      // ---- phase 1: moments -> SSIM map -> adjoint values of row r0 + p - 5 at column gxa
+      if (tid < NT1) {
+        const float* ra = sa + p * ROWF + tid;
+        const float* rb = sb + p * ROWF + tid;
+        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
 #pragma unroll
         for (int k = 0; k < WIN; k++) {
-          o0 = fmaf(WK(k), w2[(p + 1 + k) % RB][0], o0);
-          o1 = fmaf(WK(k), w2[(p + 1 + k) % RB][1], o1);
-          o2 = fmaf(WK(k), w2[(p + 1 + k) % RB][2], o2);
+          const float a = ra[3 * k], b = rb[3 * k];
+          const float ga = WK(k) * a, gb = WK(k) * b;
+          m1 += ga; m2 += gb;
+          e11 = fmaf(ga, a, e11); e22 = fmaf(gb, b, e22); e12 = fmaf(ga, b, e12);
         }
-        if (own_col && gx < W) {
-          const size_t pidx = ((size_t)gy * W + gx) * 3 + c;
-          v_img[pidx] = weight * (o0 + 2.f * img[pidx] * o1 + gt[pidx] * o2);
+        w[p][0] = m1; w[p][1] = m2; w[p][2] = e11; w[p][3] = e22; w[p][4] = e12;
+        const int gy = r0 + p - HALO;                // map / adjoint row
+        float A = 0.f, B = 0.f, C = 0.f;
+        if (gy >= ys - HALO && gy < ye + HALO && gy >= 0 && gy < H) {      // uniform
+          float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int k = 0; k < WIN; k++) {
+#pragma unroll
+            for (int q = 0; q < 5; q++) o[q] = fmaf(WK(k), w[(p + 1 + k) % RB][q], o[q]);
+          }
+          const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+          const float mu1 = o[0], mu2 = o[1];
+          const float s11 = o[2] - mu1 * mu1, s22 = o[3] - mu2 * mu2, s12 = o[4] - mu1 * mu2;
+          const float n1 = 2.f * mu1 * mu2 + C1, n2 = 2.f * s12 + C2;
+          const float d1 = mu1 * mu1 + mu2 * mu2 + C1, d2 = s11 + s22 + C2;
+          const float id1 = __builtin_amdgcn_rcpf(d1), id2 = __builtin_amdgcn_rcpf(d2);
+          const float m = n1 * n2 * id1 * id2;
+          if (adj_in) {
+            if (own_col && gy >= ys && gy < ye && gy >= c_lo && gy < c_hi) msum += m;
+            const float dm_ds12 = 2.f * n1 * id1 * id2;
+            const float dm_ds11 = -m * id2;
+            const float dm_dmu1 = 2.f * mu2 * n2 * id1 * id2 - m * 2.f * mu1 * id1;
+            A = dm_dmu1 - 2.f * mu1 * dm_ds11 - mu2 * dm_ds12;
+            B = dm_ds11;
+            C = dm_ds12;
+          }
+        }
+        float* o3 = sadj + (p & 1) * ADJF + tid * 3;
+        o3[0] = A; o3[1] = B; o3[2] = C;
+      }
+      __syncthreads();                               // the row is in LDS; every wave is done with the row before the last
+      // ---- phase 2: filtered adjoint maps -> v_img of row r0 + p - 10 at column gxo (adjoint columns col .. col + 10)
+      if (tid < NT2) {
+        const float* r = sadj + (p & 1) * ADJF + tid * 3;
+        float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < WIN; k++) {
+          h0 = fmaf(WK(k), r[9 * k], h0);
+          h1 = fmaf(WK(k), r[9 * k + 1], h1);
+          h2 = fmaf(WK(k), r[9 * k + 2], h2);
+        }
+        w2[p][0] = h0; w2[p][1] = h1; w2[p][2] = h2;
+        if (gyo >= ys && gyo < ye) {                 // uniform
+          float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+#pragma unroll
+          for (int k = 0; k < WIN; k++) {
+            o0 = fmaf(WK(k), w2[(p + 1 + k) % RB][0], o0);
+            o1 = fmaf(WK(k), w2[(p + 1 + k) % RB][1], o1);
+            o2 = fmaf(WK(k), w2[(p + 1 + k) % RB][2], o2);
+          }
+          if (out_in) {
+            const ptrdiff_t orow = (ptrdiff_t)gyo * W * 3 + (ptrdiff_t)x0 * 3;     // uniform
+            (v_img + orow)[ut] = weight * (o0 + 2.f * (img + orow)[ut] * o1 + (gt + orow)[ut] * o2);
+          }
         }
       }
     }
   }
-  const float tot = wave_sum(msum);
+  // the sum of adjoint column col + 5 = output column col goes to the thread that owns that output column in k_ssim_fwd
+  __syncthreads();
+  sa[tid] = msum;
+  __syncthreads();
+  const float tot = wave_sum(tid < NT2 ? sa[tid + 3 * HALO] : 0.f);
   if ((tid & 63) == 0) red[tid >> 6] = tot;
   __syncthreads();
   const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
-  if (tid == 0) block_partials[wg] = red[0] + red[1] + red[2];
-  for (int i = nwg + wg * NTH + tid; i < n_partials; i += nwg * NTH) block_partials[i] = 0.f;
+  if (tid == 0) block_partials[wg] = red[0] + red[1] + red[2];   // (the fourth wave holds no output column)
+  for (int i = nwg + wg * FT + tid; i < n_partials; i += nwg * FT) block_partials[i] = 0.f;
 }
 
 // No forward row to produce (an empty band): nothing counts, but the caller still sums block_partials.  A kernel rather
@@ -459,8 +495,19 @@ __global__ void k_ssim_zero_partials(float* __restrict__ block_partials, int n_p
 
 }  // namespace
 
-// the fused kernel counts a map pixel in the workgroup that owns its output row: the counted rows must be output rows
+// the one-pass kernel counts a map pixel in the workgroup that owns its output row: the counted rows must be output rows
 static inline bool count_inside(int y0, int y1, int c0, int c1) { return c0 >= c1 || (c0 >= y0 && c1 <= y1); }
+
+// Which kernels a gradient call runs (tgs_set_ssim_form; environment TGS_SSIM_FUSED, read once at first use):
+//   0  k_ssim_fwd + k_ssim_bwd, the adjoint planes in `scratch`
+//   1  one pass on the kernel's own grid: 54-column strips, segments of 11 nblk - 20 rows from y0
+//   2  one pass on the two-kernel path's grid (64-column strips, the forward launch's segments): the same block_partials,
+//      bit for bit
+//   3  (default) 2 where it is the faster one, 0 elsewhere
+enum { SSIM_TWO_KERNELS = 0, SSIM_ONE_PASS_OWN_GRID = 1, SSIM_ONE_PASS = 2, SSIM_AUTO = 3 };
+static TgsDefault g_ssim_form{"TGS_SSIM_FUSED", SSIM_AUTO, false, SSIM_AUTO};
+// SSIM_AUTO: the one-pass kernel from this many pixels on (1080p; see DESIGN 5.4 for the sizes below it)
+constexpr long long SSIM_ONE_PASS_MIN_PIXELS = 1920LL * 1080;
 
 static int ssim_impl(int W, int H, const float* img, const float* gt, float weight,
                      float* block_partials, int n_partials, float* v_img, float* scratch,
@@ -474,15 +521,14 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
   for (int i = 0; i < WIN; i++) { g[i] = exp(-(double)((i - HALO) * (i - HALO)) / (2.0 * 1.5 * 1.5)); sum += g[i]; }
   for (int i = 0; i < WIN; i++) win.g[i] = (float)(g[i] / sum);
   static const int env_nblk = [] { const char* e = getenv("TGS_SSIM_NBLK"); return e ? max(2, min(16, atoi(e))) : 0; }();
-  // TGS_SSIM_FUSED=1 selects the one-pass kernel.  Default 0: measured SLOWER (1080p 119 against 108 us alone, 104 against 100
-  // inside the step, profiles/r5_ssim_one_pass.txt) although it moves half the bytes (171 against 343 MB, PMC) -- the two kernels are not
-  // HBM-bound (3.3 TB/s), and the one-pass form pays 1.5x the forward arithmetic (halo) at 3 workgroups per CU (45 KB of LDS)
-  static const int env_fused = [] { const char* e = getenv("TGS_SSIM_FUSED"); return e ? atoi(e) : 0; }();
-  if (v_img && env_fused && y1 > y0 && count_inside(y0, y1, c0, c1)) {
-    // one pass, adjoint planes on chip (k_ssim_fused); `scratch` is not touched.  Strip = 54 columns x (11 nblk - 20) rows:
-    // long segments keep the vertical halo small ((SEG + 20) / SEG input rows, (SEG + 10) / SEG of the forward arithmetic);
-    // the kernel holds 3 workgroups per CU (LDS), so the longest segment that still gives every slot a workgroup is taken
-    const int fx = (W + SWO - 1) / SWO;
+  int form = g_ssim_form.get();
+  if (form == SSIM_AUTO) form = (long long)W * H >= SSIM_ONE_PASS_MIN_PIXELS ? SSIM_ONE_PASS : SSIM_TWO_KERNELS;
+  const bool one_pass = v_img && y1 > y0 && count_inside(y0, y1, c0, c1);
+  if (one_pass && form == SSIM_ONE_PASS_OWN_GRID) {
+    // `scratch` is not touched.  Strip = 54 columns x (11 nblk - 20) rows: long segments keep the vertical halo small
+    // ((SEG + 20) / SEG input rows, (SEG + 10) / SEG of the forward arithmetic); the longest segment that still gives
+    // 600 workgroups is taken
+    const int fx = (W + SWO_OWN - 1) / SWO_OWN;
     auto wgs = [&](int nb) { return (long long)fx * ((y1 - y0 + fused_seg_rows(nb) - 1) / fused_seg_rows(nb)); };
     int nblk = 7;
     while (nblk > 3 && wgs(nblk) < 600) nblk--;
@@ -490,8 +536,8 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
     while (nblk < 16 && wgs(nblk) > n_partials) nblk++;
     TGS_CHECK_ARG(wgs(nblk) <= n_partials, "block_partials too small");
     const int SEGF = fused_seg_rows(nblk);
-    hipLaunchKernelGGL(k_ssim_fused, dim3(fx, (y1 - y0 + SEGF - 1) / SEGF, 1), dim3(NTH), 0, (hipStream_t)stream, W, H, weight,
-                       img, gt, v_img, block_partials, n_partials, nblk, y0, y1, c0, c1);
+    hipLaunchKernelGGL(k_ssim_fused<SWO_OWN>, dim3(fx, (y1 - y0 + SEGF - 1) / SEGF, 1), dim3(FT), 0, (hipStream_t)stream, W, H,
+                       weight, img, gt, v_img, block_partials, n_partials, SEGF, y0, y0, y1, c0, c1);
     TGS_CHECK_LAUNCH();
     return TGS_OK;
   }
@@ -517,6 +563,14 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
   const int SEG = seg_rows(nblk);
   const dim3 block(NTH);
   hipStream_t s = (hipStream_t)stream;
+  if (one_pass && form == SSIM_ONE_PASS) {
+    // the forward launch's grid: a workgroup writes the rows of its segment that lie in [y0, y1) and the sum k_ssim_fwd's
+    // workgroup of the same index would
+    hipLaunchKernelGGL(k_ssim_fused<SW>, dim3(sx, (rows + SEG - 1) / SEG, 1), dim3(FT), 0, s, W, H, weight, img, gt, v_img,
+                       block_partials, n_partials, SEG, f0, y0, y1, c0, c1);
+    TGS_CHECK_LAUNCH();
+    return TGS_OK;
+  }
   hipLaunchKernelGGL(k_ssim_fwd, dim3(sx, (rows + SEG - 1) / SEG, 1), block, 0, s, W, H, win, img, gt,
                      v_img ? scratch : nullptr, block_partials, n_partials, nblk, f0, f1, c0, c1);
   TGS_CHECK_LAUNCH();
@@ -542,4 +596,9 @@ extern "C" int tgs_ssim_fwd_bwd_rows(int W, int H, const float* img, const float
                                      void* stream) {
   return ssim_impl(W, H, img, gt, weight, block_partials, n_partials, v_img, scratch, y0, y1, count_y0,
                    count_y1, stream);
+}
+
+extern "C" int tgs_set_ssim_form(int form) {
+  if (form >= 0) g_ssim_form.set(form);
+  return g_ssim_form.get();
 }
