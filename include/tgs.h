@@ -396,6 +396,24 @@ int tgs_project_bwd(const TgsCamera* cam /*[host]*/, int N, const float* means,
                     float* v_sh, float* v_xy,
                     const int32_t* skip_if_overflow /*status[2] of the frame, or NULL*/, void* stream);
 
+/* Camera-pose gradient: dL/dV of rows 0-2 of the world->camera matrix, V = [R | p] (camera refinement).
+ *     A stand-alone pair of launches beside K8: it reads what tgs_project_bwd reads (the same two input forms: partials
+ *     + group_base, or v_splats with partials NULL; sh may be NULL) BEFORE the optimizer changes the parameters, and
+ *     changes nothing but its two outputs.  No atomics, bit-reproducible; no host synchronisation.
+ * out[TGS_POSE_OUT]: [0..11] the raw 3x4 gradient, row-major like viewmat rows 0-2 (G_R | G_p);
+ *     [12..23] per entry the sum of the absolute values of the products that form it (the unit of its rounding error);
+ *     [24] 1 = valid, 0 = the frame was void (skip_if_overflow[1] != 0: everything else is 0 too);
+ *     [25] number of visible Gaussians (exact below 2^24); [26..31] 0.
+ * block_scratch[tgs_num_groups(N), TGS_POSE_ROW]: one row per 256-Gaussian group = the 24 values above and the group's
+ *     count of visible Gaussians; overwritten. */
+#define TGS_POSE_ROW 25
+#define TGS_POSE_OUT 32
+int tgs_pose_grad(const TgsCamera* cam /*[host]*/, int N, const float* means, const float* log_scales,
+                  const float* quats, const float* sh, int sh_stride, int sh_deg, const float* splats,
+                  const int32_t* group_base, const float* partials /*or NULL*/, const float* v_splats /*or NULL*/,
+                  float* block_scratch, float* out,
+                  const int32_t* skip_if_overflow /*status[2] of the frame, or NULL*/, void* stream);
+
 /* K8+K9 fused (single-process training): projection/SH backward whose gradients go straight
  *     through the Adam update of the flat parameter buffer `params` (layout of TgsAdamSpec) and
  *     its moment buffers -- the 59-float gradient of a Gaussian never touches HBM.  Requires an

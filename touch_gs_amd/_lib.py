@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("TGS_LIB_PATH") or os.path.join(_HERE, "lib", "libtgs_
 SPLAT_FLOATS = 12
 PARTIAL_FLOATS = 12
 GROUP = 256
+POSE_ROW = 25     # TGS_POSE_ROW: floats per group in the scratch of tgs_pose_grad
+POSE_OUT = 32     # TGS_POSE_OUT
 BLOCK = 16
 
 
@@ -93,6 +95,7 @@ SIGNATURES = {
     "tgs_rasterize_bwd_band": (C.c_int, [C.POINTER(TgsCamera)] + [_P] * 4 + [C.c_int64] + [_P] * 8 + [C.POINTER(TgsLossSpec), _P, _P, _I, _P, C.POINTER(TgsRasterOpts), _P]),
     "tgs_reduce_partials": (C.c_int, [_I, _P, _P, C.POINTER(TgsCamera), _P, _P, _P]),
     "tgs_project_bwd": (C.c_int, [C.POINTER(TgsCamera), _I, _P, _P, _P, _P, _P, _I, _I] + [_P] * 12),
+    "tgs_pose_grad": (C.c_int, [C.POINTER(TgsCamera), _I, _P, _P, _P, _P, _I, _I] + [_P] * 8),
     "tgs_project_bwd_adam": (C.c_int, [C.POINTER(TgsCamera), _I, _I, _I, _P, _P, _P, C.POINTER(TgsAdamSpec), _P, _P, _P, _P, _P, _P]),
     "tgs_project_bwd_adam_next": (C.c_int, [C.POINTER(TgsCamera), _I, _I, _I, _P, _P, _P, C.POINTER(TgsAdamSpec), _P, _P, _P,
                                             _P, _P, C.POINTER(TgsCamera), _P, _P, C.c_int32, _P]),

@@ -425,7 +425,8 @@ FLAG_SETS = {
 
 def train_and_eval(root: str, flags: str, with_depth: bool, iters: int = 30000, out_dir: Optional[str] = None,
                    num_gaussians: int = 100000, extra_args: Sequence[str] = (), seed: int = 0, device="cuda",
-                   split: Optional[float] = None, percent_take: Optional[float] = None, preset: str = "few-view") -> dict:
+                   split: Optional[float] = None, percent_take: Optional[float] = None, preset: str = "few-view",
+                   view_hook=None) -> dict:
     """``ns-train depth-gaussian-splatting`` + ``run_eval`` of one reference flag set on a prepared capture:
     seeds for the flag set's split (create_point_cloud_from_touches), ``touch_gs_amd.train`` for ``iters`` iterations
     with or without the depth term, ``touch_gs_amd.run_eval`` under IS_REAL_WORLD (scripts/train_bunny_real.sh:54), and
@@ -450,7 +451,7 @@ def train_and_eval(root: str, flags: str, with_depth: bool, iters: int = 30000, 
             "--seed", str(seed), "--preset", preset, *extra_args]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_dir = train.main(argv)
+    run_dir = train.main(argv, view_hook=view_hook)      # view_hook: see train.main
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     was = os.environ.get("IS_REAL_WORLD")

@@ -640,10 +640,17 @@ __global__ __launch_bounds__(256) void k_reduce_partials(
   st4(o + 8, make_float4(v[8], v[9], 0.f, 0.f));
 }
 
+// What the camera-pose gradient (k_pose_grad) takes out of geom_bwd: dL/dt of the camera-space mean (every path, clamp
+// gates included), dL/dTm of the 2x3 projected-covariance factor Tm = J R, and J's four non-constant entries J00, J02, J11,
+// J12 as geom_eval forms them.
+struct PoseTerms { float vt[3], vTm[6], J[4]; };
+
 // B.8 geometry backward for one visible Gaussian: v = {v_x, v_y, v_depth, -, v_a, v_b, v_c, ...}
-// -> accumulates into vm (means), writes vls (log-scales) and vq (quaternion).
+// -> accumulates into vm (means), writes vls (log-scales) and vq (quaternion).  POSE: also hands out `pt`; the K8 kernels
+// instantiate POSE = false, whose code is what it was before the parameter existed.
+template <bool POSE = false>
 __device__ __forceinline__ void geom_bwd(const CamK& cam, const float* m, const float* ls, const float* q,
-                                         const float* v, float* vm, float* vls, float* vq) {
+                                         const float* v, float* vm, float* vls, float* vq, PoseTerms* pt = nullptr) {
     Geom G;
     geom_eval(cam, m, ls, q, G);
     const float id = 1.0f / G.det;
@@ -692,6 +699,14 @@ __device__ __forceinline__ void geom_bwd(const CamK& cam, const float* m, const 
     vt[0] += v[0] * cam.fx * rz; vt[2] += -v[0] * cam.fx * G.tx * rz2;
     vt[1] += v[1] * cam.fy * rz; vt[2] += -v[1] * cam.fy * G.ty * rz2;
     vt[2] += v[2];
+    if constexpr (POSE) {
+#pragma unroll
+      for (int j = 0; j < 3; j++) pt->vt[j] = vt[j];
+#pragma unroll
+      for (int j = 0; j < 6; j++) pt->vTm[j] = vTm[j];
+      pt->J[0] = cam.fx * rz; pt->J[1] = -cam.fx * G.ucx * rz;
+      pt->J[2] = cam.fy * rz; pt->J[3] = -cam.fy * G.ucy * rz;
+    }
 #pragma unroll
     for (int j = 0; j < 3; j++) vm[j] += R[j] * vt[0] + R[3 + j] * vt[1] + R[6 + j] * vt[2];
     // Sigma = M M^T  ->  v_M = 2 v_Sigma M,  M = Rq diag(s)
@@ -850,6 +865,145 @@ __global__ __launch_bounds__(256) void k_project_bwd(
     geom_bwd(cam, m, ls, q, v, vm, vls, vq);
   }
   store_geom_grads<true>(g, v, vm, vls, vq, vol, v_xy, v_means, v_log_scales, v_quats, v_opac_logit);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Camera-pose gradient: dL/dV of rows 0-2 of the world->camera matrix V = [R | p], beside K8
+// ---------------------------------------------------------------------------------------------
+// A stand-alone launch that reads what K8 reads and writes TGS_POSE_ROW floats per 256-Gaussian group; a step that does
+// not refine poses never issues it.  The loss reaches V through three paths:
+//   1. the camera-space mean t = R m + p:        G_p += vt,  G_R[i][j] += vt[i] m[j]        (visible Gaussians)
+//   2. the covariance factor Tm = J R:            G_R += J^T vTm                             (visible Gaussians)
+//   3. the SH view direction through campos = -R^T p, whose gradient is -vmd (vmd = what sh_color_bwd adds to the mean):
+//      G_p[i] += sum_j R[i][j] vmd[j],  G_R[i][j] += p[i] vmd[j]                             (every Gaussian, DEG >= 1)
+// Beside each of the 12 entries (row-major 3x4, like viewmat rows 0-2) goes its MASS, the sum of the absolute values of
+// the products above: the un-cancelled magnitude in which gradient errors are stated.  Slot 24 counts the visible
+// Gaussians.  No atomics: a workgroup reduces its 25 values in a fixed tree (DPP rows, two wave shuffles, the four waves
+// in order through LDS) and writes one row; k_pose_grad_final adds the rows in index order.
+template <int DEG>
+__global__ __launch_bounds__(256) void k_pose_grad(
+    CamK cam, int N, const float* __restrict__ means, const float* __restrict__ log_scales,
+    const float* __restrict__ quats, const float* __restrict__ sh, int sh_stride,
+    const float* __restrict__ splats, const int32_t* __restrict__ group_base, const float* __restrict__ partials,
+    const float* __restrict__ v_splats, float* __restrict__ block_scratch, const int32_t* __restrict__ guard) {
+  __shared__ RunScan S;
+  __shared__ float wave_sum[TGS_GROUP / TGS_WAVE][TGS_POSE_ROW];
+  // overflowed frame: the pair index space is not backed by memory (workgroup-uniform, ahead of every barrier); the
+  // final kernel reports the frame void and does not read the rows this launch has not written
+  if (guard && guard[1]) return;
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x * 256 + tid;
+  // threads past N stay to the end: group_sum_partials and the reduction need the whole workgroup; they add zeros
+  float v[10];
+  if (partials) {
+    group_sum_partials(splats, group_base, partials, g, N, v, S, cam.long_run);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 10; i++) v[i] = 0.f;
+    if (g < N) {
+      const float* p = v_splats + (size_t)g * TGS_SPLAT_FLOATS;
+      const float4 a = ld4(p), b = ld4(p + 4);
+      const float2 c = *reinterpret_cast<const float2*>(p + 8);
+      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z;
+      v[7] = b.w; v[8] = c.x; v[9] = c.y;
+    }
+  }
+  float acc[TGS_POSE_ROW];   // 4 i + j: G_R[i][j] (j < 3), G_p[i] (j = 3); + 12: the masses; 24: visible
+#pragma unroll
+  for (int i = 0; i < TGS_POSE_ROW; i++) acc[i] = 0.f;
+  if (g < N) {
+    const float m[3] = {means[3 * g], means[3 * g + 1], means[3 * g + 2]};
+    const float* R = cam.R;
+    if constexpr (DEG >= 1) {   // path 3 (degree 0 has no view dependence)
+      constexpr int K = (DEG + 1) * (DEG + 1);
+      const float* c = sh + (size_t)g * sh_stride * 3;
+      float ck[3 * K], Y[16], vr[3], vmd[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int i = 0; i < 3 * K; i++) ck[i] = c[i];
+      sh_color_bwd<DEG>(m, cam.campos, ck, v, Y, vr, vmd);
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          const float a = R[3 * i + j] * vmd[j], b = cam.t[i] * vmd[j];
+          acc[4 * i + 3] += a; acc[12 + 4 * i + 3] += fabsf(a);
+          acc[4 * i + j] += b; acc[12 + 4 * i + j] += fabsf(b);
+        }
+    }
+    // paths 1 and 2: only of a Gaussian that passed the culls (K8's own test); 1 / det and 1 / tz are not finite otherwise
+    if (splats[(size_t)g * TGS_SPLAT_FLOATS + 4] > 0.f) {
+      float ls[3], q[4], vm[3] = {0.f, 0.f, 0.f}, vls[3], vq[4];
+      load_scale_quat(log_scales, quats, g, ls, q);
+      PoseTerms pt;
+      geom_bwd<true>(cam, m, ls, q, v, vm, vls, vq, &pt);
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        acc[4 * i + 3] += pt.vt[i]; acc[12 + 4 * i + 3] += fabsf(pt.vt[i]);
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          const float a = pt.vt[i] * m[j];
+          acc[4 * i + j] += a; acc[12 + 4 * i + j] += fabsf(a);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 3; j++) {   // J^T vTm: row 0 from J00, row 1 from J11, row 2 from J02 and J12
+        const float a0 = pt.J[0] * pt.vTm[j], a1 = pt.J[2] * pt.vTm[3 + j];
+        const float a2 = pt.J[1] * pt.vTm[j], b2 = pt.J[3] * pt.vTm[3 + j];
+        acc[j] += a0; acc[12 + j] += fabsf(a0);
+        acc[4 + j] += a1; acc[16 + j] += fabsf(a1);
+        acc[8 + j] += a2; acc[20 + j] += fabsf(a2);
+        acc[8 + j] += b2; acc[20 + j] += fabsf(b2);
+      }
+      acc[24] = 1.f;
+    }
+  }
+  // all 256 lanes are here (no early exit above but the uniform guard): rows of 16 by DPP, the wave's four rows by shuffles
+#pragma unroll
+  for (int i = 0; i < TGS_POSE_ROW; i++) {
+    float s = row_sum16(acc[i]);
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    acc[i] = s;
+  }
+  if ((tid & (TGS_WAVE - 1)) == 0) {
+#pragma unroll
+    for (int i = 0; i < TGS_POSE_ROW; i++) wave_sum[tid / TGS_WAVE][i] = acc[i];
+  }
+  __syncthreads();
+  if (tid < TGS_POSE_ROW) {
+    float s = wave_sum[0][tid];
+#pragma unroll
+    for (int w = 1; w < TGS_GROUP / TGS_WAVE; w++) s += wave_sum[w][tid];
+    block_scratch[(size_t)blockIdx.x * TGS_POSE_ROW + tid] = s;
+  }
+}
+
+// One workgroup: the G rows in index order (staged 256 rows at a time through LDS, coalesced), then out[32] =
+// G[12] | mass[12] | valid | #visible | 0...; a void frame (overflow) gives all zeros and reads no row.
+__global__ __launch_bounds__(256) void k_pose_grad_final(int G, const float* __restrict__ block_scratch,
+                                                         float* __restrict__ out, const int32_t* __restrict__ guard) {
+  __shared__ float rows[256 * TGS_POSE_ROW];
+  const int tid = threadIdx.x;
+  if (guard && guard[1]) {
+    if (tid < TGS_POSE_OUT) out[tid] = 0.f;
+    return;
+  }
+  float acc = 0.f;
+  int cnt = 0;
+  for (int r0 = 0; r0 < G; r0 += 256) {   // G is uniform: every thread meets every barrier
+    const int nr = min(256, G - r0);
+    for (int i = tid; i < nr * TGS_POSE_ROW; i += 256) rows[i] = block_scratch[(size_t)r0 * TGS_POSE_ROW + i];
+    __syncthreads();
+    if (tid < 24) {
+      for (int r = 0; r < nr; r++) acc += rows[r * TGS_POSE_ROW + tid];
+    } else if (tid == 24) {
+      for (int r = 0; r < nr; r++) cnt += (int)rows[r * TGS_POSE_ROW + 24];
+    }
+    __syncthreads();
+  }
+  if (tid < 24) out[tid] = acc;
+  else if (tid == 24) { out[24] = 1.f; out[25] = (float)cnt; }
+  else if (tid >= 26 && tid < TGS_POSE_OUT) out[tid] = 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1238,6 +1392,35 @@ extern "C" int tgs_project_bwd(const TgsCamera* cam, int N, const float* means,
                      v_log_scales, v_quats, v_opac_logit, v_sh, (float*)nullptr, v_xy, skip_if_overflow)
   DISPATCH_DEG_OR_NONE(LAUNCH, sh_deg);
 #undef LAUNCH
+  TGS_CHECK_LAUNCH();
+  return TGS_OK;
+}
+
+extern "C" int tgs_pose_grad(const TgsCamera* cam, int N, const float* means, const float* log_scales,
+                             const float* quats, const float* sh, int sh_stride, int sh_deg,
+                             const float* splats, const int32_t* group_base, const float* partials,
+                             const float* v_splats, float* block_scratch, float* out,
+                             const int32_t* skip_if_overflow, void* stream) {
+  TGS_CHECK_ARG(camera_ok(cam), "bad camera");
+  TGS_CHECK_ARG(N >= 0, "N < 0");
+  TGS_CHECK_ARG(out, "null output pointer");
+  if (!sh) sh_deg = -1;
+  TGS_CHECK_ARG(sh_deg <= 3, "sh_deg > 3");
+  TGS_CHECK_ARG(sh_deg < 0 || sh_stride >= (sh_deg + 1) * (sh_deg + 1), "sh_stride too small");
+  const int G = (N + 255) / 256;
+  hipStream_t s = (hipStream_t)stream;
+  if (N > 0) {
+    TGS_CHECK_ARG(means && log_scales && quats && splats && block_scratch, "null pointer");
+    TGS_CHECK_ARG((partials && group_base) || v_splats, "need partials+group_base or v_splats");
+    const CamK k = make_camk(cam);
+#define LAUNCH(D)                                                                                       \
+  hipLaunchKernelGGL(k_pose_grad<D>, dim3(G), dim3(256), 0, s, k, N, means, log_scales, quats, sh,      \
+                     sh_stride, splats, group_base, partials, v_splats, block_scratch, skip_if_overflow)
+    DISPATCH_DEG_OR_NONE(LAUNCH, sh_deg);
+#undef LAUNCH
+    TGS_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_pose_grad_final, dim3(1), dim3(256), 0, s, G, block_scratch, out, skip_if_overflow);
   TGS_CHECK_LAUNCH();
   return TGS_OK;
 }

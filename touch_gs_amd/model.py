@@ -96,6 +96,14 @@ class ModelConfig:
     # (optim.balanced_order): a layout choice like the Morton order itself, results unchanged
     balance_long_runs: bool = True
     long_run: int = 0          # tiles beyond which a Gaussian is a long run (Camera.long_run); 0 = chosen at every re-sort (32, or 8 for object-centric frames)
+    # camera pose refinement (touch_gs_amd.pose): Adam learning rates of the per-view rotation (radians) and
+    # translation (scene units) in the camera frame.  Both 0 = off: no launch, nothing changes.  pose_l2_*: pull of the
+    # accumulated change towards the original pose; pose_start_step: the first step that produces a pose gradient
+    pose_lr_rot: float = 0.0
+    pose_lr_trans: float = 0.0
+    pose_l2_rot: float = 0.0
+    pose_l2_trans: float = 0.0
+    pose_start_step: int = 0
 
     def downscale_factor(self, step: int) -> int:
         """2 ** max(num_downscales - step // resolution_schedule, 0)  (Splatfacto._get_downscale_factor)."""
@@ -161,6 +169,12 @@ class View:
             self.n_valid_depth = int((self.depth > 0).sum().item()) if self.depth is not None else 0
         return self.n_valid_depth
 
+    def set_camera(self, cam: Camera) -> None:
+        """Replace the camera (pose refinement), also under the cached downscaled forms of this view."""
+        self.cam = cam
+        for d, v in self.__dict__.get("_downscaled", {}).items():
+            v.cam = cam.downscaled(d)
+
     def downscaled(self, d: int) -> "View":
         """This view at 1/d of its resolution (cached): the colour image resized bilinearly to (H // d, W // d) --
         what Splatfacto's ``_downscale_if_required`` does (torchvision resize of a tensor, no antialiasing) --
@@ -207,6 +221,23 @@ class DepthGaussianSplattingModel:
         self.last = {}
         self.tuning = Tuning()      # until the first re-sort that has seen a frame: the process defaults
         self._tuned_cams = {}
+        self.pose_refiner = None    # enable_pose_refinement(views)
+        self._pose_scratch = None
+
+    def enable_pose_refinement(self, views):
+        """Refine the poses of ``views`` (the full-resolution TRAINING views; held-out views are not given) with the
+        learning rates of the config; -> the PoseRefiner, or None when both rates are 0."""
+        c = self.config
+        if c.pose_lr_rot <= 0 and c.pose_lr_trans <= 0:
+            self.pose_refiner = None
+            return None
+        if getattr(self, "_graphs", None):
+            raise ValueError("pose refinement (pose_lr_rot / pose_lr_trans) does not combine with capture_step_graphs: a "
+                             "captured graph bakes the camera in")
+        from .pose import PoseRefiner
+        self.pose_refiner = PoseRefiner(views, c.pose_lr_rot, c.pose_lr_trans, l2_rot=c.pose_l2_rot, l2_trans=c.pose_l2_trans,
+                                        model=self)
+        return self.pose_refiner
 
     def tuned(self, cam: Camera, keep: bool = True) -> Camera:
         """``cam`` carrying this model's ``tuning.long_run``: what every launch of the model is given, so that K1's
@@ -336,6 +367,10 @@ class DepthGaussianSplattingModel:
             valid = view.depth > 0
             d = outputs["depth"][..., 0]
             m["depth_mse"] = ((d - view.depth)[valid] ** 2).mean() if valid.any() else torch.tensor(0.0)
+        if self.pose_refiner is not None:   # mean change of the refined poses against the originals
+            dl = self.pose_refiner.deltas()
+            m["pose_delta_deg"] = torch.tensor(sum(a for a, _ in dl) / max(len(dl), 1))
+            m["pose_delta_m"] = torch.tensor(sum(b for _, b in dl) / max(len(dl), 1))
         return m
 
     @torch.no_grad()
@@ -402,9 +437,11 @@ class DepthGaussianSplattingModel:
 
     def forward_backward(self, view: View, want_v_xy: bool = False, fuse_adam: bool = False,
                          color_block: Optional[torch.Tensor] = None, begin_step: bool = True,
-                         colors=None, prefetch=None, next_front=None):
+                         colors=None, prefetch=None, next_front=None, pose_grad: bool = False):
         """Forward + loss + backward of one view into ``params.grad`` (overwritten) -- or, with
         ``fuse_adam``, straight through the optimizer update (K8+K9 fused, ``params.grad`` untouched).
+        ``pose_grad``: also ``last["pose_grad"]`` = ``ops.pose_grad`` of this frame, launched before the optimizer
+        kernel changes the parameters it was rendered with.
         No host sync unless ``budget.sync``.  Returns device tensors (l1+depth tile losses, ssim sum)."""
         p, c, cam = self.params, self.config, self.tuned(view.cam)
         deg = self.active_sh_degree()
@@ -444,6 +481,16 @@ class DepthGaussianSplattingModel:
             partials, tile_loss = ops.rasterize_bwd(cam, splats, group_base, sorted_gid, tile_start, rgb,
                                                     depth_acc, fT, v_rgb=v_img, v_depth=v_depth, v_alpha=v_alpha,
                                                     loss=self.loss_spec(view), want_tile_loss=True)
+        pose_out = None
+        if pose_grad:
+            if color_block is not None:
+                raise ValueError("pose refinement (pose_lr_rot / pose_lr_trans) is not supported in data-parallel steps")
+            G = ops._lib.load().tgs_num_groups(p.N)
+            if self._pose_scratch is None or self._pose_scratch.shape[0] < G or self._pose_scratch.device != p.flat.device:
+                self._pose_scratch = torch.empty(max(G, 1), ops._lib.POSE_ROW, dtype=torch.float32, device=p.flat.device)
+            pose_out = ops.pose_grad(cam, p.means, p.log_scales, p.quats, p.sh, deg, splats, group_base, partials,
+                                     guard=guard, out=(torch.empty(ops._lib.POSE_OUT, dtype=torch.float32, device=p.flat.device),
+                                                       self._pose_scratch))
         if fuse_adam:
             v_xy = self.optimizer.backward_and_step(cam, deg, splats, group_base, partials, want_v_xy,
                                                     begin=begin_step, guard=guard, prefetch=prefetch)
@@ -468,6 +515,8 @@ class DepthGaussianSplattingModel:
                                    group_base, partials, out=p.grad_views(), want_v_xy=want_v_xy, guard=guard)[5]
         self.last = dict(rgb=rgb, depth_acc=depth_acc, final_T=fT, splats=splats, v_xy=v_xy, radii=radii,
                          tile_loss=tile_loss, ssim_sum=ssim_sum, status=status, guard=guard, view=view)
+        if pose_out is not None:
+            self.last["pose_grad"] = pose_out
         if mono_stats is not None:
             self.last["mono_stats"] = mono_stats
         if patch_off is not None:
@@ -664,6 +713,8 @@ class DepthGaussianSplattingModel:
         ``last``, saving a checkpoint or evaluating when the speculative budget is on)."""
         if getattr(self, "_pending", None) is not None and self.budget.speculative:
             self._speculative_poll(drain=True)
+        if self.pose_refiner is not None:
+            self.pose_refiner.flush(self)
 
     # -- hipGraph replay of the step (small scenes are launch bound) ----------------------------
     def capture_step_graphs(self, views, headroom: float = 1.3, share_pool: bool = True) -> None:
@@ -676,6 +727,9 @@ class DepthGaussianSplattingModel:
         views (x ``headroom``) and the overflow flag is checked lazily (``budget.check``).
         Graphs are dropped when the active SH degree or the number of Gaussians changes."""
         opt, deg = self.optimizer, self.active_sh_degree()
+        if self.pose_refiner is not None or self.config.pose_lr_rot > 0 or self.config.pose_lr_trans > 0:
+            raise ValueError("capture_step_graphs does not combine with pose refinement (pose_lr_rot / pose_lr_trans): a "
+                             "captured graph bakes the camera in")
         if not opt.can_fuse_with_backward(deg):
             raise RuntimeError("step graphs need the fused K8+K9 path (dense SH at its full degree 1 or 3)")
         p = self.params
@@ -712,6 +766,21 @@ class DepthGaussianSplattingModel:
         between the two calls except through this class."""
         distributed = dp is not None and dp.active
         opt = self.optimizer
+        ref, pose_on = self.pose_refiner, False
+        if ref is None and (self.config.pose_lr_rot > 0 or self.config.pose_lr_trans > 0):
+            raise ValueError("pose_lr_rot / pose_lr_trans are set but no view is registered for refinement: call "
+                             "model.enable_pose_refinement(training_views) before the first train_step")
+        if ref is not None:
+            if distributed:
+                raise ValueError("pose refinement (pose_lr_rot / pose_lr_trans) is not supported in data-parallel steps (dp.active)")
+            if next_view is view:      # its gradient is produced in this very step: nothing can be built ahead for it
+                next_view = None
+            # pending updates land before the view is used -- and before next_cam is armed, so that the prefetch is
+            # built for the pose the view will really have (cameras are recognised by identity)
+            ref.apply_pending(view, self)
+            if next_view is not None:
+                ref.apply_pending(next_view, self)
+            pose_on = ref.owns(view) and self.step >= self.config.pose_start_step
         if self.config.balance_long_runs and self.config.spatial_sort:
             # the cameras of the last steps (full resolution), for the next spatial_sort (host-side bookkeeping only)
             rc = self.__dict__.setdefault("_recent_cams", collections.OrderedDict())
@@ -800,8 +869,10 @@ class DepthGaussianSplattingModel:
             arm = (bufs[1] if pre is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget, colors_valid=False)
         self.forward_backward(view, want_v_xy=density is not None, fuse_adam=fuse, color_block=block,
                               colors=colors, prefetch=arm if fuse else None,
-                              next_front=arm.front if arm is not None else None)
+                              next_front=arm.front if arm is not None else None, pose_grad=pose_on)
         self._prefetch_ready = arm
+        if pose_on:     # taken at the (possibly downscaled) camera, applied to the full-resolution view's pose
+            ref.submit(full_view, self.last["pose_grad"])
         if density is not None and not factored:
             # a frame that overflowed its intersection buffer (sync-free budget) rendered nothing and will be
             # replayed: it must not count as a view (guard = its status word, evaluated on the device)
@@ -896,8 +967,11 @@ class DepthGaussianSplattingModel:
 
     # -- checkpoint -----------------------------------------------------------------------------
     def state_dict(self):
-        return dict(flat=self.params.flat, N=self.params.N, K=self.params.K, step=self.step,
-                    optim=self.optimizer.state_dict(), config=dataclasses.asdict(self.config))
+        sd = dict(flat=self.params.flat, N=self.params.N, K=self.params.K, step=self.step,
+                  optim=self.optimizer.state_dict(), config=dataclasses.asdict(self.config))
+        if self.pose_refiner is not None:   # only then: checkpoints of runs without refinement keep their keys
+            sd["pose"] = self.pose_refiner.state_dict(self)
+        return sd
 
     def load_state_dict(self, sd):
         """Restores parameters, Adam state and the step counter.  A checkpoint written after
@@ -918,6 +992,8 @@ class DepthGaussianSplattingModel:
         self._prefetch_ready = None
         self.step = sd["step"]
         self.optimizer.load_state_dict(sd["optim"])
+        if self.pose_refiner is not None and sd.get("pose") is not None:
+            self.pose_refiner.load_state_dict(sd["pose"], self)
 
 
 class _SSIM(torch.autograd.Function):

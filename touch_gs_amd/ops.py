@@ -602,6 +602,35 @@ def project_bwd(cam: Camera, means, log_scales, quats, opac_logit, sh, sh_deg, s
     return v_means, v_ls, v_q, v_ol, v_sh, v_xy
 
 
+def pose_grad(cam: Camera, means, log_scales, quats, sh, sh_deg, splats, group_base=None, partials=None,
+              v_splats=None, guard=None, out=None):
+    """Gradient of the loss w.r.t. rows 0-2 of ``cam.viewmat`` -> device tensor [32] = G[3,4] row-major | the 12
+    masses (sum of |products| per entry) | valid flag | number of visible Gaussians | zeros.  (tgs_pose_grad)
+
+    Reads what :func:`project_bwd` reads (``partials`` + ``group_base``, or ``v_splats``) and writes nothing else, so
+    it must run BEFORE an optimizer step that changes the parameters of the frame.  ``sh=None``: no colour path (the
+    colours did not come from SH rows).  ``guard`` = the frame's status word: an overflowed frame gives all zeros.
+    No host synchronisation, no allocation when ``out`` = (result [32], scratch [groups, 25]) is passed: safe under
+    stream capture."""
+    lib = _lib.load()
+    N = means.shape[0]
+    dev = means.device
+    if out is None:
+        out = (torch.empty(_lib.POSE_OUT, dtype=torch.float32, device=dev),
+               torch.empty(max(lib.tgs_num_groups(N), 1), _lib.POSE_ROW, dtype=torch.float32, device=dev))
+    res, scratch = out
+    if res.numel() != _lib.POSE_OUT or scratch.numel() < lib.tgs_num_groups(N) * _lib.POSE_ROW:
+        raise ValueError("pose_grad: out = (float32 [32], float32 [tgs_num_groups(N), 25])")
+    if partials is None and v_splats is None:
+        raise ValueError("pose_grad needs partials (+ group_base) or v_splats")
+    cs = cam.c_struct()
+    sh_stride = sh.shape[1] if sh is not None else 0
+    check(lib.tgs_pose_grad(C.byref(cs), N, ptr(means), ptr(log_scales), ptr(quats), ptr(sh), sh_stride,
+                            sh_deg if sh is not None else -1, ptr(splats), ptr(group_base), ptr(partials),
+                            ptr(v_splats), ptr(scratch), ptr(res), ptr(guard), _stream()), "tgs_pose_grad")
+    return res
+
+
 def project_bwd_color(cam: Camera, means, log_scales, quats, opac_logit, sh, sh_deg, splats, group_base,
                       partials, out, v_color, want_v_xy=False, guard=None, rows=None, v_xy=None):
     """K8 of the data-parallel step (tgs_project_bwd_color): geometry gradients into ``out`` =
@@ -761,7 +790,8 @@ def record_xy(splats: torch.Tensor) -> torch.Tensor:
 
 class _ProjectGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3d, scales, glob_scale, quats, cam):
+    def forward(ctx, means3d, scales, glob_scale, quats, cam, viewmat=None):
+        # viewmat: the caller's world->camera tensor when it asks for its gradient (the values are cam's), else None
         means3d, quats = _f32c(means3d), _f32c(quats)
         log_scales = torch.log(_f32c(scales))
         N = means3d.shape[0]
@@ -791,7 +821,11 @@ class _ProjectGaussians(torch.autograd.Function):
         v_means, v_ls, v_q, _, _, _ = project_bwd(ctx.cam, means3d, log_scales, quats, zero, None, -1,
                                                   splats, v_splats=v_splats)
         v_scales = v_ls / torch.exp(log_scales)
-        return v_means, v_scales, None, v_q, None
+        v_view = None
+        if ctx.needs_input_grad[5]:   # camera pose: rows 0-2 from tgs_pose_grad (no colour path: viewdirs are torch's own)
+            G = pose_grad(ctx.cam, means3d, log_scales, quats, None, -1, splats, v_splats=v_splats)
+            v_view = torch.cat([G[:12].view(3, 4), G.new_zeros(1, 4)], 0)
+        return v_means, v_scales, None, v_q, None, v_view
 
 
 def project_gaussians(means3d, scales, glob_scale, quats, viewmat, fx, fy, cx, cy, img_height,
@@ -805,7 +839,9 @@ def project_gaussians(means3d, scales, glob_scale, quats, viewmat, fx, fy, cx, c
     if block_width != 16:
         raise ValueError("only 16x16 tiles are supported (SURVEY App. B.0)")
     cam = Camera(viewmat, fx, fy, cx, cy, img_width, img_height, near=clip_thresh)
-    xys, depths, radii, conics = _ProjectGaussians.apply(means3d, scales, glob_scale, quats, cam)
+    want_pose = torch.is_tensor(viewmat) and viewmat.requires_grad
+    xys, depths, radii, conics = _ProjectGaussians.apply(means3d, scales, glob_scale, quats, cam,
+                                                         viewmat if want_pose else None)
     with torch.no_grad():
         tw, th = cam.tiles
         r = radii.to(torch.float32)

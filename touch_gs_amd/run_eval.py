@@ -60,6 +60,8 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
         scene = Scene(cfg["data"], cfg["train_split_fraction"], device,
                       normal_dir=(normal_dir or cfg.get("normal_dir")) if normals else None,
                       normal_frame=normal_frame or cfg.get("normal_frame") or "opencv")
+        from .pose import apply_refined_poses
+        apply_refined_poses(run_dir, scene.views, scene.names)   # training views as the run left them (held-out ones are not listed)
         idx = list(scene.i_eval) or list(scene.i_train)[:1]
         views, names, scale = [scene.views[i] for i in idx], [scene.names[i] for i in idx], scene.scale
     results = evaluate(model, views, depth_stats=depth_stats, normals=normals)

@@ -141,7 +141,9 @@ def render_views(model: DepthGaussianSplattingModel, views, out_dir: str, names=
                         uncertainty_png(out["depth_var"].reshape(v.cam.H, v.cam.W), dataparser_scale))
 
 
-def main(argv=None):
+def main(argv=None, view_hook=None):
+    """``view_hook(train_views, dataparser_scale)``, if given, is called once the training views are loaded and before anything
+    is built on them (experiments that edit the views in memory, e.g. tools/pose_refine_quality.py); not a command-line option."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", type=str, default=None)
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("N", "W", "H"), default=None)
@@ -222,6 +224,13 @@ def main(argv=None):
     ap.add_argument("--refine-every", type=int, default=100)
     ap.add_argument("--warmup-length", type=int, default=500)
     ap.add_argument("--densify-grad-thresh", type=float, default=0.0002)
+    ap.add_argument("--pose-lr-rot", type=float, default=0.0,
+                    help="camera pose refinement of the TRAINING views: Adam learning rate of the rotation (radians, camera "
+                         "frame); 0 with --pose-lr-trans 0 = off (the default under both presets)")
+    ap.add_argument("--pose-lr-trans", type=float, default=0.0, help="... of the translation (scene units)")
+    ap.add_argument("--pose-l2-rot", type=float, default=0.0, help="pull of the accumulated rotation towards the original pose")
+    ap.add_argument("--pose-l2-trans", type=float, default=0.0, help="... of the accumulated translation")
+    ap.add_argument("--pose-start-step", type=int, default=0, help="first step that refines poses")
     args = ap.parse_args(argv)
 
     few = args.preset == "few-view"
@@ -261,8 +270,16 @@ def main(argv=None):
                       mono_depth_alpha_min=args.mono_depth_alpha_min, mono_depth_local_mult=args.mono_depth_local_mult,
                       mono_depth_patch_tiles=args.mono_depth_patch_tiles, mono_depth_patch_min_fill=args.mono_depth_patch_min_fill,
                       mono_depth_patch_min_var=args.mono_depth_patch_min_var, normal_prior_mult=args.normal_mult,
-                      normal_max_jump=args.normal_max_jump)
+                      normal_max_jump=args.normal_max_jump, pose_lr_rot=args.pose_lr_rot, pose_lr_trans=args.pose_lr_trans,
+                      pose_l2_rot=args.pose_l2_rot, pose_l2_trans=args.pose_l2_trans, pose_start_step=args.pose_start_step)
     model = DepthGaussianSplattingModel(cfg, params)
+    train_views = [views[i] for i in i_train]
+    train_names = [f"view_{i}" for i in i_train] if args.synthetic else [scene.names[i] for i in i_train]
+    if (cfg.pose_lr_rot > 0 or cfg.pose_lr_trans > 0) and dp.active:
+        raise ValueError("--pose-lr-rot / --pose-lr-trans: pose refinement is not supported in data-parallel runs")
+    if view_hook is not None:
+        view_hook(train_views, 1.0 if args.synthetic else scene.scale)
+    model.enable_pose_refinement(train_views)     # held-out views are never refined; before a checkpoint is loaded
     if cfg.spatial_sort:
         model.spatial_sort()
     if args.densify:
@@ -301,7 +318,6 @@ def main(argv=None):
         # agree on it on the device and replay the same steps)
         # TGS_SPEC_CAPACITY: test hook -- an initial capacity far too small forces the overflow / replay path
         model.enable_speculative_budget(capacity=int(os.environ.get("TGS_SPEC_CAPACITY", "0")))
-    train_views = [views[i] for i in i_train]
     eval_views = [views[i] for i in i_eval] or train_views[:1]
     t0 = time.time()
     seen_refine, n_refines = None, 0
@@ -330,6 +346,9 @@ def main(argv=None):
                 print(f"   held-out: " + " ".join(f"{a}={b:.5g}" for a, b in r.items()), flush=True)
         if dp.rank == 0 and at_save:
             torch.save(dict(model.state_dict(), trainer=trainer_state), os.path.join(run_dir, f"step-{step + 1:09d}.ckpt"))
+            if model.pose_refiner is not None:
+                from .pose import save_refined_poses
+                save_refined_poses(run_dir, model.pose_refiner, train_names)
     model.flush()
     if dp.world > 1:
         dp.assert_replicas_identical(model.params.flat)
