@@ -672,6 +672,35 @@ int tgs_depth_normal_fwd_bwd(const TgsCamera* cam, const float* out_depth, const
                              float* normals /*may be NULL*/, float* v_depth /*may be NULL*/, float* v_alpha /*may be NULL*/,
                              int accumulate, void* stream);
 
+/* Per-view exposure compensation  C' = A C + b  (an ADDITION within TGS_VERSION 320: no struct and no earlier signature
+ *     changes; csrc/exposure.hip).  E = [A | b] is row-major 3x4 in DEVICE memory, the identity = no change;
+ *     rgb [H,W,3] is tgs_rasterize_fwd's out_rgb (background included); there is no clamp.
+ * tgs_exposure_fwd: rgb_out[p][c] = sum_k A[c][k] rgb[p][k] + b[c].  One launch.
+ * tgs_exposure_bwd: the RGB loss is taken on C' (recomputed here with the forward's bits, not read):
+ *         v'[p][c] = v_img[p][c] + l1_weight * sign(C'[p][c] - gt[p][c]),  sign(0) = 0   (tgs_rasterize_bwd's fused L1 term);
+ *     gt NULL = no L1 term, v_img NULL = no upstream image (e.g. SSIM's gradient with respect to C'), both NULL = zeros.
+ *     v_rgb[p][k] = sum_c A[c][k] v'[p][c]: the upstream image tgs_rasterize_bwd takes, with TgsLossSpec.gt_rgb = NULL.
+ *     out[TGS_EXPO_OUT]: [0..11] G = dL/dE row-major 3x4, G_A[c][k] = sum_p v'[p][c] rgb[p][k], G_b[c] = sum_p v'[p][c];
+ *         [12..23] per entry the sum of the absolute values of those products (the unit of its rounding error);
+ *         [24] 1 = valid, 0 = the frame was void (guard[1] != 0: everything else is 0 too, `state` keeps every bit);
+ *         [25] l1_weight * sum |C' - gt|;  [26] W * H;  [27..31] 0.
+ *     partials[tgs_exposure_num_partials(W, H), TGS_EXPO_OUT]: scratch, one row per workgroup; overwritten.
+ *     state[TGS_EXPO_STATE] or NULL (gradient only): one view's optimizer row {[0..11] E, [12..23] exp_avg, [24..35]
+ *         exp_avg_sq, [36] steps taken t, [37] beta1^t, [38] beta2^t (running products; 1 at t = 0), [39..47] 0}.  On a valid frame
+ *         g = G + l2 (E - I), t and the products advance, and the 12 entries take one Adam step (the update of
+ *         tgs_adam_step) with the bias corrections 1 - state[37], 1 - state[38].  expo may be state itself: the row is written
+ *         by the last launch only.
+ *     Three launches in all, no float atomics: the same inputs give the same bits.  No host synchronisation. */
+#define TGS_EXPO_OUT   32   /* floats of the result */
+#define TGS_EXPO_STATE 48   /* floats of one view's state row */
+int tgs_exposure_num_partials(int W, int H);   /* workgroup rows of the scratch; a function of W, H alone */
+int tgs_exposure_fwd(int W, int H, const float* rgb, const float* expo /*device [12]*/, float* rgb_out, void* stream);
+int tgs_exposure_bwd(int W, int H, const float* rgb, const float* expo /*device [12]*/,
+                     const float* gt /*may be NULL*/, float l1_weight, const float* v_img /*may be NULL*/,
+                     float* v_rgb, float* partials /*[num_partials, 32]*/, float* out /*[32]*/,
+                     const int32_t* guard /*may be NULL*/, float* state /*[48] or NULL = gradient only*/,
+                     float lr, float beta1, float beta2, float eps, float l2, void* stream);
+
 /* A Gaussian-process implicit surface (GPIS) ray-marched into one view: touch depth, posterior variance and surface normal
  *     (an ADDITION within TGS_VERSION 320: a new struct and a new call, nothing earlier changes; csrc/gpis.hip).
  *     The device form of touch_gs_amd.gpis.GPIS.render_depth, which stays the definition.

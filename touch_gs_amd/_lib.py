@@ -14,6 +14,9 @@ PARTIAL_FLOATS = 12
 GROUP = 256
 POSE_ROW = 25     # TGS_POSE_ROW: floats per group in the scratch of tgs_pose_grad
 POSE_OUT = 32     # TGS_POSE_OUT
+EXPO_OUT = 32     # TGS_EXPO_OUT: floats of tgs_exposure_bwd's result and of a row of its scratch
+EXPO_STATE = 48   # TGS_EXPO_STATE: floats of one view's exposure row (E | exp_avg | exp_avg_sq | t, beta1^t, beta2^t | 0...)
+EXPO_CHUNK = 2048  # pixels per workgroup of k_expo_bwd_tiles (csrc/exposure.hip): tgs_exposure_num_partials = ceil(W H / it)
 BLOCK = 16
 
 
@@ -125,6 +128,9 @@ SIGNATURES = {
                                               _P, _P, _P, _P, _P, _P]),
     "tgs_depth_normal_fwd_bwd": (C.c_int, [C.POINTER(TgsCamera), _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P,
                                           _P, _I, _P]),
+    "tgs_exposure_num_partials": (C.c_int, [_I, _I]),
+    "tgs_exposure_fwd": (C.c_int, [_I, _I, _P, _P, _P, _P]),
+    "tgs_exposure_bwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P]),
     "tgs_gpis_render": (C.c_int, [_I, _P, _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.POINTER(TgsGpisView), _P, _P, _P, _P, _P]),
     "tgs_tsdf_integrate": (C.c_int, [_I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, C.POINTER(TgsTsdfView), _P]),
     "tgs_tsdf_extract_count": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, C.c_float, _P, _P]),

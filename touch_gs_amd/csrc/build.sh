@@ -6,7 +6,7 @@ OUT="$HERE/../lib"
 mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wall -Wno-unused-function $TGS_EXTRA_FLAGS"
-SRCS="api project binning raster optim imgloss depthcorr depthnormal gpis tsdf peer"
+SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gpis tsdf peer"
 # raster.hip: the SLP vectoriser pairs the per-pixel FMAs into v_pk_fma_f32, which on gfx950 costs
 # 1.84x a plain v_fma_f32 and needs register-pair shuffles (v_mov) around it: K7 127 -> 100 VGPRs and
 # -7 % time, K6 -3 % without it (measured, same box)
@@ -18,10 +18,12 @@ SRCS="api project binning raster optim imgloss depthcorr depthnormal gpis tsdf p
 # optimizer kernel (front prefetch), and the two must produce the same bits.
 # depthnormal.hip: -ffp-contract=on for the same reason: dnorm_centre is inlined into the forward and the gradient kernel,
 # which must form the same normals and decide |m| > 0 alike.
+# exposure.hip: -ffp-contract=on for the same reason: expo_apply is inlined into the forward and into the backward, which
+# recomputes the compensated image instead of reading it and must form the bits SSIM saw, so that sign() decides alike.
 # tsdf.hip: -ffp-contract=off: every product and sum rounds on its own, as the fp32 NumPy emulation of tests/tsdf_ref.py
 # evaluates them (the emulation's measured error is then the kernel's); the kernels are HBM-bound.
 declare -A EXTRA=([raster]="-fno-slp-vectorize" [imgloss]="-fno-slp-vectorize" [project]="-ffp-contract=on"
-                  [depthnormal]="-ffp-contract=on" [tsdf]="-ffp-contract=off")
+                  [depthnormal]="-ffp-contract=on" [exposure]="-ffp-contract=on" [tsdf]="-ffp-contract=off")
 pids=()
 for s in $SRCS; do
   [ -f "$HERE/$s.hip" ] || continue

@@ -104,6 +104,12 @@ class ModelConfig:
     pose_l2_rot: float = 0.0
     pose_l2_trans: float = 0.0
     pose_start_step: int = 0
+    # per-view exposure compensation (touch_gs_amd.exposure): Adam learning rate of the 3x4 affine colour
+    # transform of every registered training view.  0 = off: no launch, nothing changes.  exposure_l2: pull of E towards
+    # the identity; exposure_start_step: the first step that compensates (and learns)
+    exposure_lr: float = 0.0
+    exposure_l2: float = 0.0
+    exposure_start_step: int = 0
 
     def downscale_factor(self, step: int) -> int:
         """2 ** max(num_downscales - step // resolution_schedule, 0)  (Splatfacto._get_downscale_factor)."""
@@ -223,6 +229,21 @@ class DepthGaussianSplattingModel:
         self._tuned_cams = {}
         self.pose_refiner = None    # enable_pose_refinement(views)
         self._pose_scratch = None
+        self.exposure_set = None    # enable_exposure(views)
+
+    def enable_exposure(self, views):
+        """Learn an exposure matrix for each of ``views`` (the full-resolution TRAINING views; held-out views are not
+        given and are rendered uncompensated) with the rate of the config; -> the ExposureSet, or None when the rate is 0."""
+        c = self.config
+        if c.exposure_lr <= 0:
+            self.exposure_set = None
+            return None
+        if getattr(self, "_graphs", None):
+            raise ValueError("exposure compensation (exposure_lr) does not combine with capture_step_graphs: the captured "
+                             "step has no exposure launches")
+        from .exposure import ExposureSet
+        self.exposure_set = ExposureSet(views, self.params.flat.device, c.exposure_lr, l2=c.exposure_l2)
+        return self.exposure_set
 
     def enable_pose_refinement(self, views):
         """Refine the poses of ``views`` (the full-resolution TRAINING views; held-out views are not given) with the
@@ -266,8 +287,12 @@ class DepthGaussianSplattingModel:
         return min((self.step if step is None else step) // c.sh_degree_interval, c.sh_degree, max_deg)
 
     def get_outputs(self, cam: Camera, sh_degree: Optional[int] = None, depth_stats: bool = False,
-                    normals: bool = False) -> Dict[str, torch.Tensor]:
+                    normals: bool = False, exposure_of: Optional["View"] = None) -> Dict[str, torch.Tensor]:
         """Camera -> {rgb, depth, accumulation} (differentiable; autograd path).
+
+        ``exposure_of``: a full-resolution training view; where it owns an exposure row (``enable_exposure``), ``rgb`` is
+        the compensated image ``ops.apply_exposure(rgb, E)`` (differentiable in the scene; E is a constant here) and
+        ``rgb_raw`` the rendered one.  Any other view, and the default call, give the rendered image.
 
         ``normals=True`` adds ``normal`` [H,W,3]: the unit normals of the rendered depth in the camera's OpenCV axes
         (ops.depth_normals with the config's normal_alpha_min / normal_max_jump; exactly 0 where none is formed), detached.
@@ -301,6 +326,9 @@ class DepthGaussianSplattingModel:
         if normals:
             out["normal"] = ops.depth_normals(cam, depth_acc, 1.0 - alpha.detach(), self.config.normal_alpha_min,
                                               self.config.normal_max_jump)
+        if exposure_of is not None and self.exposure_set is not None and self.exposure_set.owns(exposure_of):
+            E = self.exposure_set.row(exposure_of)[:12].detach().clone().view(3, 4)
+            out.update(rgb_raw=rgb, rgb=ops.apply_exposure(rgb, E))
         return out
 
     def depth_loss(self, depth_acc, alpha, view: View) -> torch.Tensor:
@@ -320,10 +348,17 @@ class DepthGaussianSplattingModel:
     def get_loss_dict(self, outputs, view: View) -> Dict[str, torch.Tensor]:
         c = self.config
         H, W = view.rgb.shape[:2]
-        l1 = (outputs["rgb"] - view.rgb).abs().mean()
+        rgb = outputs["rgb"]
+        es = self.exposure_set
+        if es is not None and es.owns(view) and self.step >= c.exposure_start_step and "rgb_raw" not in outputs:
+            # the autograd path of the exposure term: the loss is taken on the compensated image; E is a leaf whose
+            # gradient the caller may read from outputs["exposure"].grad (the fused step learns it on the device)
+            E = outputs["exposure"] = es.row(view)[:12].detach().clone().view(3, 4).requires_grad_(True)
+            rgb = ops.apply_exposure(rgb, E)
+        l1 = (rgb - view.rgb).abs().mean()
         loss = {"main_loss": (1 - c.ssim_lambda) * l1}
         if c.ssim_lambda > 0:
-            loss["main_loss"] = loss["main_loss"] + c.ssim_lambda * (1 - _SSIM.apply(outputs["rgb"], view.rgb))
+            loss["main_loss"] = loss["main_loss"] + c.ssim_lambda * (1 - _SSIM.apply(rgb, view.rgb))
         if c.depth_loss_mult > 0 and view.depth is not None:
             loss["depth_loss"] = c.depth_loss_mult * self.depth_loss(outputs["depth_acc"], outputs["alpha"], view)
         if self.mono_depth_local_active(view):
@@ -371,6 +406,10 @@ class DepthGaussianSplattingModel:
             dl = self.pose_refiner.deltas()
             m["pose_delta_deg"] = torch.tensor(sum(a for a, _ in dl) / max(len(dl), 1))
             m["pose_delta_m"] = torch.tensor(sum(b for _, b in dl) / max(len(dl), 1))
+        if self.exposure_set is not None and len(self.exposure_set.views) > 0:   # means over the training views
+            E = self.exposure_set.state[:, :12]
+            m["exposure_gain"] = E[:, [0, 5, 10]].mean()
+            m["exposure_offset"] = E[:, [3, 7, 11]].mean()
         return m
 
     @torch.no_grad()
@@ -437,11 +476,15 @@ class DepthGaussianSplattingModel:
 
     def forward_backward(self, view: View, want_v_xy: bool = False, fuse_adam: bool = False,
                          color_block: Optional[torch.Tensor] = None, begin_step: bool = True,
-                         colors=None, prefetch=None, next_front=None, pose_grad: bool = False):
+                         colors=None, prefetch=None, next_front=None, pose_grad: bool = False,
+                         exposure: Optional[torch.Tensor] = None):
         """Forward + loss + backward of one view into ``params.grad`` (overwritten) -- or, with
         ``fuse_adam``, straight through the optimizer update (K8+K9 fused, ``params.grad`` untouched).
         ``pose_grad``: also ``last["pose_grad"]`` = ``ops.pose_grad`` of this frame, launched before the optimizer
         kernel changes the parameters it was rendered with.
+        ``exposure``: the [48] row of the view's exposure (``ExposureSet.row``): the RGB loss is taken on the compensated
+        image C' = A rgb + b -- ``ops.exposure_fwd``, SSIM on C', ``ops.exposure_bwd`` (which forms the L1 term, hands K7
+        its upstream image and steps the row), K7 without its fused L1 term -- and ``last["exposure"]`` = its [32] result.
         No host sync unless ``budget.sync``.  Returns device tensors (l1+depth tile losses, ssim sum)."""
         p, c, cam = self.params, self.config, self.tuned(view.cam)
         deg = self.active_sh_degree()
@@ -468,7 +511,24 @@ class DepthGaussianSplattingModel:
             normal_stats, _, v_depth, v_alpha = ops.depth_normal_fwd_bwd(
                 cam, depth_acc, fT, view.normal_prior, view.normal_conf, c.normal_alpha_min, c.normal_max_jump,
                 weight=c.normal_prior_mult, accumulate_into=None if mono_stats is None else (v_depth, v_alpha))
-        if (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles and mono_stats is None
+        expo_out = None
+        if exposure is not None:
+            if color_block is not None:
+                raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps")
+            es = self.exposure_set
+            spec = self.loss_spec(view)
+            rgb_c = ops.exposure_fwd(rgb, exposure)
+            if c.ssim_lambda > 0:
+                ssim_sum, v_img = ops.ssim_fwd_bwd(rgb_c, view.rgb, weight=-c.ssim_lambda / (3 * H * W), reduce=False)
+            expo_out, v_rgb = ops.exposure_bwd(rgb, exposure, gt=view.rgb, l1_weight=spec["l1_weight"], v_img=v_img,
+                                               guard=guard, state=exposure, adam=es.adam,
+                                               out=(torch.empty(ops._lib.EXPO_OUT, dtype=torch.float32, device=rgb.device),
+                                                    es.scratch(W, H)))
+            spec.update(gt_rgb=None, l1_weight=0.0)     # the L1 term went in through v_rgb; the depth terms stay fused
+            partials, tile_loss = ops.rasterize_bwd(cam, splats, group_base, sorted_gid, tile_start, rgb,
+                                                    depth_acc, fT, v_rgb=v_rgb, v_depth=v_depth, v_alpha=v_alpha,
+                                                    loss=spec, want_tile_loss=True)
+        elif (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles and mono_stats is None
                 and normal_stats is None and not torch.cuda.is_current_stream_capturing()):
             if getattr(self, "_side_stream", None) is None:
                 self._side_stream = torch.cuda.Stream(device=rgb.device)
@@ -517,6 +577,8 @@ class DepthGaussianSplattingModel:
                          tile_loss=tile_loss, ssim_sum=ssim_sum, status=status, guard=guard, view=view)
         if pose_out is not None:
             self.last["pose_grad"] = pose_out
+        if expo_out is not None:
+            self.last["exposure"] = expo_out
         if mono_stats is not None:
             self.last["mono_stats"] = mono_stats
         if patch_off is not None:
@@ -525,13 +587,20 @@ class DepthGaussianSplattingModel:
             self.last["normal_stats"] = normal_stats
         return tile_loss, ssim_sum
 
-    def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None) -> Dict[str, torch.Tensor]:
+    def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None, exposure=None) -> Dict[str, torch.Tensor]:
         """The loss values of a fused step from what ``forward_backward`` returned.  ``mono_stats``: the statistics of the
-        monocular depth term; default = those of the last ``forward_backward`` when ``tile_loss`` is that call's."""
+        monocular depth term; default = those of the last ``forward_backward`` when ``tile_loss`` is that call's.
+        ``exposure``: the [32] result of the step's ``ops.exposure_bwd`` (``last["exposure"]``) when the step compensated the
+        view's exposure -- its L1 value is then in that result, not in ``tile_loss``; the same default.  A caller that
+        keeps a ``tile_loss`` beyond its step, or passes a copy of it, keeps and passes that step's ``last["exposure"]`` too."""
         c = self.config
         H, W = view.rgb.shape[:2]
         t = tile_loss.sum(0)
         main = t[0]
+        if exposure is None and self.last.get("tile_loss") is tile_loss:
+            exposure = self.last.get("exposure")
+        if exposure is not None:
+            main = main + exposure[25]     # the L1 term was taken on the compensated image: K7's column is 0
         if ssim_sum is not None:   # per-block partial sums (or an already reduced scalar)
             main = main + c.ssim_lambda * (1 - ssim_sum.sum() / (3 * H * W))
         out = {"main_loss": main, "depth_loss": t[1]}
@@ -730,6 +799,9 @@ class DepthGaussianSplattingModel:
         if self.pose_refiner is not None or self.config.pose_lr_rot > 0 or self.config.pose_lr_trans > 0:
             raise ValueError("capture_step_graphs does not combine with pose refinement (pose_lr_rot / pose_lr_trans): a "
                              "captured graph bakes the camera in")
+        if self.exposure_set is not None or self.config.exposure_lr > 0:
+            raise ValueError("capture_step_graphs does not combine with exposure compensation (exposure_lr): the captured "
+                             "step has no exposure launches")
         if not opt.can_fuse_with_backward(deg):
             raise RuntimeError("step graphs need the fused K8+K9 path (dense SH at its full degree 1 or 3)")
         p = self.params
@@ -781,6 +853,15 @@ class DepthGaussianSplattingModel:
             if next_view is not None:
                 ref.apply_pending(next_view, self)
             pose_on = ref.owns(view) and self.step >= self.config.pose_start_step
+        es, expo_row = self.exposure_set, None
+        if es is None and self.config.exposure_lr > 0:
+            raise ValueError("exposure_lr is set but no view is registered for exposure compensation: call "
+                             "model.enable_exposure(training_views) before the first train_step")
+        if es is not None:
+            if distributed:
+                raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps (dp.active)")
+            if es.owns(view) and self.step >= self.config.exposure_start_step:
+                expo_row = es.row(view)     # of the full-resolution view: its downscaled forms step the same row
         if self.config.balance_long_runs and self.config.spatial_sort:
             # the cameras of the last steps (full resolution), for the next spatial_sort (host-side bookkeeping only)
             rc = self.__dict__.setdefault("_recent_cams", collections.OrderedDict())
@@ -869,7 +950,7 @@ class DepthGaussianSplattingModel:
             arm = (bufs[1] if pre is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget, colors_valid=False)
         self.forward_backward(view, want_v_xy=density is not None, fuse_adam=fuse, color_block=block,
                               colors=colors, prefetch=arm if fuse else None,
-                              next_front=arm.front if arm is not None else None, pose_grad=pose_on)
+                              next_front=arm.front if arm is not None else None, pose_grad=pose_on, exposure=expo_row)
         self._prefetch_ready = arm
         if pose_on:     # taken at the (possibly downscaled) camera, applied to the full-resolution view's pose
             ref.submit(full_view, self.last["pose_grad"])
@@ -971,6 +1052,8 @@ class DepthGaussianSplattingModel:
                   optim=self.optimizer.state_dict(), config=dataclasses.asdict(self.config))
         if self.pose_refiner is not None:   # only then: checkpoints of runs without refinement keep their keys
             sd["pose"] = self.pose_refiner.state_dict(self)
+        if self.exposure_set is not None:   # likewise
+            sd["exposure"] = self.exposure_set.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -994,6 +1077,10 @@ class DepthGaussianSplattingModel:
         self.optimizer.load_state_dict(sd["optim"])
         if self.pose_refiner is not None and sd.get("pose") is not None:
             self.pose_refiner.load_state_dict(sd["pose"], self)
+        # a model WITHOUT a set ignores the key on purpose: evaluation and export load a compensated run's checkpoint
+        # and render every view uncompensated (held-out views have no row); a set of another size is refused by the set
+        if self.exposure_set is not None and sd.get("exposure") is not None:
+            self.exposure_set.load_state_dict(sd["exposure"])
 
 
 class _SSIM(torch.autograd.Function):

@@ -1155,3 +1155,101 @@ def depth_normal_loss(cam: Camera, depth_acc, alpha, prior, conf=None, alpha_min
     (:func:`depth_normal_fwd_bwd`), a device scalar differentiable in ``depth_acc`` and ``alpha`` with validity, the gates and
     the weight sum held constant; ``depth_acc`` / ``alpha`` as :func:`render` returns them.  No host sync."""
     return _DepthNormalLoss.apply(depth_acc, alpha, prior, conf, cam, alpha_min, max_jump)
+
+
+# ------------------------------------------------------------------------------------------------
+# per-view exposure compensation C' = A C + b (csrc/exposure.hip, DESIGN 5.1n)
+# ------------------------------------------------------------------------------------------------
+def _expo_row(expo, what: str):
+    """The 12 floats E = [A | b] (row-major 3x4) a kernel reads: a [3,4] / [12] tensor, or the head of a [48] state row."""
+    if not expo.is_cuda or expo.dtype != torch.float32 or not expo.is_contiguous() or expo.numel() < 12:
+        raise ValueError(f"{what}: expo must be a contiguous float32 device tensor of at least 12 elements")
+    return expo
+
+
+def _expo_buf(t, n: int, what: str, dev, dtype=torch.float32, exact: bool = False):
+    """A buffer a kernel writes (or the guard it reads): on the frame's device, contiguous, of the dtype and size it assumes."""
+    if (not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or not t.is_contiguous()
+            or (t.numel() != n if exact else t.numel() < n)):
+        raise ValueError(f"exposure_bwd: {what} must be a contiguous {dtype} tensor on {dev} of "
+                         f"{'' if exact else 'at least '}{n} elements")
+    return t
+
+
+def exposure_fwd(rgb, expo, out=None):
+    """-> C' [H,W,3] with C'[p][c] = sum_k A[c][k] rgb[p][k] + b[c]; ``expo`` = E = [A | b] on the device ([3,4], [12] or a
+    view's [48] state row).  No clamp.  No host sync.  (tgs_exposure_fwd)"""
+    lib = _lib.load()
+    rgb = _f32c(rgb.detach())
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"exposure_fwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    H, W = rgb.shape[0], rgb.shape[1]
+    if out is None:
+        out = torch.empty_like(rgb)
+    elif out.device != rgb.device or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != rgb.shape:
+        raise ValueError("exposure_fwd: out must be a contiguous float32 tensor of rgb's shape on rgb's device")
+    check(lib.tgs_exposure_fwd(W, H, ptr(rgb), ptr(_expo_row(expo, "exposure_fwd")), ptr(out), _stream()), "tgs_exposure_fwd")
+    return out
+
+
+def exposure_bwd(rgb, expo, gt=None, l1_weight: float = 0.0, v_img=None, guard=None, state=None, adam=None, out=None):
+    """The backward of :func:`exposure_fwd` with the L1 term taken on C' -> (out32, v_rgb).  (tgs_exposure_bwd)
+
+    ``v' = v_img + l1_weight * sign(C' - gt)`` (either image may be None), ``v_rgb = A^T v'`` is the upstream image
+    :func:`rasterize_bwd` takes (with a loss spec WITHOUT ``gt_rgb``), ``out32`` = G [3,4] row-major | its 12 masses | valid
+    flag | ``l1_weight * sum |C' - gt|`` | pixel count | zeros.  ``guard`` = the frame's status word: an overflowed frame
+    gives all zeros and leaves ``state`` alone.  ``state`` = a view's [48] row (:class:`touch_gs_amd.exposure.ExposureSet`),
+    stepped in the same call with ``adam = dict(lr, betas, eps, l2)``; None = gradient only.  ``expo`` may be ``state``.
+    ``out`` = (result [32], scratch [tgs_exposure_num_partials, 32]) to allocate nothing but ``v_rgb``.  No host sync."""
+    lib = _lib.load()
+    rgb, gt, v_img = _f32c(rgb.detach()), _f32c(gt), _f32c(v_img)
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"exposure_bwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    for name, t in (("gt", gt), ("v_img", v_img)):
+        if t is not None and t.shape != rgb.shape:
+            raise ValueError(f"exposure_bwd: {name} {tuple(t.shape)} does not match rgb {tuple(rgb.shape)}")
+    H, W = rgb.shape[0], rgb.shape[1]
+    dev = rgb.device
+    P = lib.tgs_exposure_num_partials(W, H)
+    if out is None:
+        out = (torch.empty(_lib.EXPO_OUT, dtype=torch.float32, device=dev),
+               torch.empty(P, _lib.EXPO_OUT, dtype=torch.float32, device=dev))
+    res, scratch = out
+    _expo_buf(res, _lib.EXPO_OUT, "out[0] (the result)", dev, exact=True)
+    _expo_buf(scratch, P * _lib.EXPO_OUT, "out[1] (the scratch, [tgs_exposure_num_partials(W, H), 32])", dev)
+    if guard is not None:
+        _expo_buf(guard, 2, "guard (the frame's status word)", dev, dtype=torch.int32)
+    lr = b1 = b2 = eps = l2 = 0.0
+    if state is not None:
+        if adam is None:
+            raise ValueError("exposure_bwd: a state row needs adam = dict(lr, betas, eps, l2)")
+        _expo_buf(state, _lib.EXPO_STATE, "state (a view's row)", dev, exact=True)
+        lr, (b1, b2), eps, l2 = adam["lr"], adam.get("betas", (0.9, 0.999)), adam.get("eps", 1e-15), adam.get("l2", 0.0)
+    v_rgb = torch.empty_like(rgb)
+    check(lib.tgs_exposure_bwd(W, H, ptr(rgb), ptr(_expo_row(expo, "exposure_bwd")), ptr(gt), C.c_float(l1_weight), ptr(v_img),
+                               ptr(v_rgb), ptr(scratch), ptr(res), ptr(guard), ptr(state), C.c_float(lr), C.c_float(b1),
+                               C.c_float(b2), C.c_float(eps), C.c_float(l2), _stream()), "tgs_exposure_bwd")
+    return res, v_rgb
+
+
+class _ApplyExposure(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgb, E):
+        Ed = _f32c(E.detach())
+        ctx.save_for_backward(rgb.detach(), Ed)
+        return exposure_fwd(rgb, Ed)
+
+    @staticmethod
+    def backward(ctx, g):
+        rgb, Ed = ctx.saved_tensors
+        out32, v_rgb = exposure_bwd(rgb, Ed, gt=None, l1_weight=0.0, v_img=g)
+        return v_rgb, out32[:12].view(3, 4).clone()
+
+
+def apply_exposure(rgb, E):
+    """C' = A rgb + b for E = [A | b] [3,4] on the device, differentiable in ``rgb`` and ``E`` (the two kernels of
+    :func:`exposure_fwd` / :func:`exposure_bwd`): what the gsplat-shaped and INRIA-shaped surfaces compose with their own
+    losses.  No host sync."""
+    if E.shape != (3, 4):
+        raise ValueError(f"apply_exposure: E must be [3,4], got {tuple(E.shape)}")
+    return _ApplyExposure.apply(rgb, E)

@@ -231,6 +231,11 @@ def main(argv=None, view_hook=None):
     ap.add_argument("--pose-l2-rot", type=float, default=0.0, help="pull of the accumulated rotation towards the original pose")
     ap.add_argument("--pose-l2-trans", type=float, default=0.0, help="... of the accumulated translation")
     ap.add_argument("--pose-start-step", type=int, default=0, help="first step that refines poses")
+    ap.add_argument("--exposure-lr", type=float, default=0.0,
+                    help="per-view exposure compensation of the TRAINING views: Adam learning rate of each view's 3x4 affine "
+                         "colour transform (INRIA's exposure_lr is 0.01); 0 = off (the default under both presets)")
+    ap.add_argument("--exposure-l2", type=float, default=0.0, help="pull of the exposure matrices towards the identity")
+    ap.add_argument("--exposure-start-step", type=int, default=0, help="first step that compensates and learns exposures")
     args = ap.parse_args(argv)
 
     few = args.preset == "few-view"
@@ -271,15 +276,19 @@ def main(argv=None, view_hook=None):
                       mono_depth_patch_tiles=args.mono_depth_patch_tiles, mono_depth_patch_min_fill=args.mono_depth_patch_min_fill,
                       mono_depth_patch_min_var=args.mono_depth_patch_min_var, normal_prior_mult=args.normal_mult,
                       normal_max_jump=args.normal_max_jump, pose_lr_rot=args.pose_lr_rot, pose_lr_trans=args.pose_lr_trans,
-                      pose_l2_rot=args.pose_l2_rot, pose_l2_trans=args.pose_l2_trans, pose_start_step=args.pose_start_step)
+                      pose_l2_rot=args.pose_l2_rot, pose_l2_trans=args.pose_l2_trans, pose_start_step=args.pose_start_step,
+                      exposure_lr=args.exposure_lr, exposure_l2=args.exposure_l2, exposure_start_step=args.exposure_start_step)
     model = DepthGaussianSplattingModel(cfg, params)
     train_views = [views[i] for i in i_train]
     train_names = [f"view_{i}" for i in i_train] if args.synthetic else [scene.names[i] for i in i_train]
     if (cfg.pose_lr_rot > 0 or cfg.pose_lr_trans > 0) and dp.active:
         raise ValueError("--pose-lr-rot / --pose-lr-trans: pose refinement is not supported in data-parallel runs")
+    if cfg.exposure_lr > 0 and dp.active:
+        raise ValueError("--exposure-lr: exposure compensation is not supported in data-parallel runs")
     if view_hook is not None:
         view_hook(train_views, 1.0 if args.synthetic else scene.scale)
     model.enable_pose_refinement(train_views)     # held-out views are never refined; before a checkpoint is loaded
+    model.enable_exposure(train_views)            # likewise: held-out views have no row and are rendered uncompensated
     if cfg.spatial_sort:
         model.spatial_sort()
     if args.densify:
@@ -349,6 +358,9 @@ def main(argv=None, view_hook=None):
             if model.pose_refiner is not None:
                 from .pose import save_refined_poses
                 save_refined_poses(run_dir, model.pose_refiner, train_names)
+            if model.exposure_set is not None:
+                from .exposure import save_exposures
+                save_exposures(run_dir, model.exposure_set, train_names)
     model.flush()
     if dp.world > 1:
         dp.assert_replicas_identical(model.params.flat)
