@@ -713,6 +713,53 @@ def test_camera_carries_the_long_run_threshold():
     assert (lib.tgs_set_long_run(-1), lib.tgs_set_k6_split(-1), lib.tgs_set_k6_split_shape(-1, -1)) == before
 
 
+def test_capacity_after_refine_at_its_four_corners():
+    """The speculative budget after a refinement: from what the frames since the last one needed, or -- nothing seen --
+    from the old capacity; scaled by the growth of N, a shrunk N counting as no growth (ratio clamped to 1)."""
+    from touch_gs_amd.ops import capacity_after_refine
+    old_cap = 50_000
+    for seen in (0, 123_457):
+        for n_before, n_after in ((3000, 4100), (3000, 2500)):
+            ratio = max(1.0, n_after / max(n_before, 1))
+            want = int(seen * ratio * 1.25) + 4096 if seen > 0 else int(old_cap * ratio) + 4096
+            assert capacity_after_refine(seen, old_cap, n_before, n_after) == want, (seen, n_before, n_after)
+    # the same four in plain numbers: a shrunk N leaves what was seen (+ 25 % + 4096), or the old capacity (+ 4096)
+    assert capacity_after_refine(123_457, old_cap, 3000, 2500) == int(123_457 * 1.25) + 4096 == 158_417
+    assert capacity_after_refine(0, old_cap, 3000, 2500) == 54_096
+    assert capacity_after_refine(0, old_cap, 3000, 6000) == 104_096 and capacity_after_refine(1000, old_cap, 3000, 6000) == 6596
+    assert capacity_after_refine(0, old_cap, 0, 10) == 10 * old_cap + 4096      # (no Gaussians before: the guard of the division)
+
+
+MODEL_STATE = ("density", "last_refine", "speculative_replays", "_graphs", "_prefetch_ready", "_prefetch_bufs", "_side_stream",
+               "_recent_cams", "_dp", "_dp_status", "_pending", "_max_in_flight", "_pinned", "_seen_need", "_seen_longest",
+               "_good_frames", "_last_downscale", "_refined_at", "_refines_since_sort", "_backward_chunk")
+
+
+def test_model_and_view_declare_their_state():
+    """Every field the train step keeps between calls exists straight after construction (populate_modules), with the
+    value its readers used to default to; a View's downscaled forms are cached in its declared field, which stays out of
+    repr and comparison."""
+    import dataclasses
+    from touch_gs_amd import Camera
+    from touch_gs_amd.model import DepthGaussianSplattingModel, ModelConfig, View
+    from touch_gs_amd.optim import GaussianParams
+    m = DepthGaussianSplattingModel(ModelConfig(sh_degree=0), GaussianParams.allocate(512, 1, torch.device("cpu")))
+    assert [k for k in MODEL_STATE if k not in vars(m)] == []
+    assert m._pending is None and m._last_downscale is None and m.density is None and m.last_refine is None
+    assert m.speculative_replays == 0 and m._seen_need == 0 and not m._graphs and len(m._recent_cams) == 0
+    m.flush()       # the speculative budget was never enabled: nothing to settle
+    cam = Camera(np.eye(4), 50.0, 50.0, 32.0, 32.0, 64, 64)
+    v = View(cam=cam, rgb=torch.rand(64, 64, 3), depth=torch.rand(64, 64))
+    f = {x.name: x for x in dataclasses.fields(View)}["_downscaled"]
+    assert not f.repr and not f.compare and not f.init and v._downscaled == {} and "_downscaled" not in repr(v)
+    h = v.downscaled(2)
+    assert v.downscaled(1) is v and v.downscaled(2) is h and v._downscaled == {2: h} and h.rgb.shape == (32, 32, 3)
+    assert View(cam=cam, rgb=v.rgb)._downscaled is not v._downscaled        # one cache per view
+    c2 = Camera(np.eye(4), 60.0, 60.0, 32.0, 32.0, 64, 64)
+    v.set_camera(c2)
+    assert v.cam is c2 and h.cam.fx == c2.downscaled(2).fx
+
+
 def test_packed_setters_round_trip_at_the_edges_of_their_fields():
     """Every setter that packs two settings into one int returns (and its ops.* decoder reads back) exactly the setting in
     force, at 0, 1, the largest value the packing holds and one past it (clamped to the largest): a field never spills

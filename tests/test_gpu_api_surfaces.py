@@ -1718,6 +1718,46 @@ def test_front_prefetch_is_bit_identical(dev, densify, speculative):
             m.budget.check()
 
 
+def test_train_step_creates_no_attribute(dev):
+    """Every field of the model is declared at construction (populate_modules) or by its enable_* call: six train steps
+    in each form of the step -- fused with the next view announced, separate Adam, densification across a refinement
+    (and a re-sort), speculative budget across a replay, coarse-to-fine across a level -- leave ``vars(model)`` with
+    exactly the names it had before the first step."""
+    from touch_gs_amd.densify import DensifyConfig
+    from touch_gs_amd.model import DepthGaussianSplattingModel, ModelConfig
+    from touch_gs_amd.optim import GaussianParams
+    from touch_gs_amd.scene import make_view, synthetic_gaussians
+    N, W, H, deg = 3000, 128, 80, 1
+    views = [make_view(N, W, H, deg, 7, dev, view=v, n_views=4) for v in range(4)]
+    P, _ = synthetic_gaussians(N, W, H, deg, 99)
+
+    def run(announce=False, setup=None, **cfg):
+        params = GaussianParams.from_tensors(*[P[k].to(dev) for k in GaussianParams.NAMES])
+        m = DepthGaussianSplattingModel(ModelConfig(sh_degree=deg, sh_degree_interval=0, **cfg), params)
+        if setup is not None:
+            setup(m)
+        names = set(vars(m))
+        for i in range(6):
+            m.train_step(views[i % 4], next_view=views[(i + 1) % 4] if announce else None)
+        m.flush()
+        torch.cuda.synchronize()
+        assert set(vars(m)) == names, sorted(set(vars(m)) ^ names)
+        assert m.step == 6 and m.optimizer.t == 6
+        return m
+
+    m = run(announce=True)
+    assert m._prefetch_ready is not None and m._prefetch_bufs is not None
+    run(setup=lambda m: setattr(m, "fuse_adam", False))
+    m = run(setup=lambda m: m.enable_densification(DensifyConfig(
+        warmup_length=2, refine_every=4, densify_grad_thresh=1e-5, densify_size_thresh=0.02, cull_alpha_thresh=0.01,
+        reset_alpha_every=0)), spatial_sort=True, resort_every_refines=1)
+    assert m.last_refine is not None and m._refined_at == 4 and len(m._recent_cams) == 4 and m._refines_since_sort == 0
+    m = run(setup=lambda m: m.enable_speculative_budget(capacity=3000))
+    assert m.speculative_replays > 0
+    m = run(num_downscales=1, resolution_schedule=3)
+    assert m._last_downscale == 1 and m.last["rgb"].shape == (H, W, 3) and set(views[0]._downscaled) == {2}
+
+
 def test_spatial_sort_is_a_pure_relayout(dev):
     """model.spatial_sort(): Morton order of parameters + Adam moments.  The render is unchanged and a
     few train steps give the same model up to the permutation (only the order of exactly equal depths

@@ -169,6 +169,7 @@ class View:
     # (ModelConfig.normal_prior_mult)
     normal_prior: Optional[torch.Tensor] = None  # [H,W,3]
     normal_conf: Optional[torch.Tensor] = None   # [H,W]
+    _downscaled: dict = dataclasses.field(default_factory=dict, init=False, repr=False, compare=False)   # d -> downscaled(d)
 
     def valid_count(self) -> int:
         if self.n_valid_depth is None:
@@ -178,7 +179,7 @@ class View:
     def set_camera(self, cam: Camera) -> None:
         """Replace the camera (pose refinement), also under the cached downscaled forms of this view."""
         self.cam = cam
-        for d, v in self.__dict__.get("_downscaled", {}).items():
+        for d, v in self._downscaled.items():
             v.cam = cam.downscaled(d)
 
     def downscaled(self, d: int) -> "View":
@@ -188,7 +189,7 @@ class View:
         no depth (or normal) is invented across an object boundary; camera as ``Camera.downscaled``."""
         if d <= 1:
             return self
-        cache = self.__dict__.setdefault("_downscaled", {})
+        cache = self._downscaled
         if d not in cache:
             H, W = self.rgb.shape[0] // d, self.rgb.shape[1] // d
             F = torch.nn.functional
@@ -223,13 +224,26 @@ class DepthGaussianSplattingModel:
         self.dp_factored_sh = True   # data-parallel steps exchange colour gradients, not SH rows
         # single-process steps that know the next view: its K1 runs inside this step's optimizer kernel
         self.front_prefetch = os.environ.get("TGS_FRONT_PREFETCH", "1") != "0"
-        self._color_block = self._color_all = self._color_rows = None
         self.last = {}
         self.tuning = Tuning()      # until the first re-sort that has seen a frame: the process defaults
         self._tuned_cams = {}
         self.pose_refiner = None    # enable_pose_refinement(views)
         self._pose_scratch = None
         self.exposure_set = None    # enable_exposure(views)
+        # every other field the train step keeps between calls is declared HERE: no method creates an attribute
+        self.density = None         # enable_densification(): the DensityController
+        self.last_refine = self._refined_at = None      # what the last density.refine reported, and the step it ran at
+        self._recent_cams = collections.OrderedDict()   # id -> full-resolution camera of the last <= 16 steps (spatial_sort)
+        self._last_downscale = None     # coarse-to-fine factor of the previous step; None = no step yet, no change of level
+        self._graphs = {}           # capture_step_graphs: id(view) -> (graph, last, SH degree, N)
+        self._side_stream = None    # pipeline_ssim: the SSIM stream, made on first use
+        self._prefetch_ready = self._prefetch_bufs = None   # the ColorPrefetch armed for this step's view | the two that alternate
+        # factored data-parallel exchange (_exchange_buffers): the rank's block, its all-gathered image, their per-chunk views
+        self._color_block = self._color_all = self._color_rows = self._color_blocks = self._color_blocks_all = None
+        self._backward_chunk = None     # K8 of one row chunk, left by forward_backward for the pipelined exchange
+        self._dp = self._dp_status = None   # this step's GradSync if data parallel | device {0, any rank overflowed}
+        self._pending, self._max_in_flight, self._pinned = None, 4, []      # speculative budget; `_pending is None` = never enabled
+        self._seen_need = self._seen_longest = self._good_frames = self.speculative_replays = self._refines_since_sort = 0
 
     def enable_exposure(self, views):
         """Learn an exposure matrix for each of ``views`` (the full-resolution TRAINING views; held-out views are not
@@ -238,7 +252,7 @@ class DepthGaussianSplattingModel:
         if c.exposure_lr <= 0:
             self.exposure_set = None
             return None
-        if getattr(self, "_graphs", None):
+        if self._graphs:
             raise ValueError("exposure compensation (exposure_lr) does not combine with capture_step_graphs: the captured "
                              "step has no exposure launches")
         from .exposure import ExposureSet
@@ -252,7 +266,7 @@ class DepthGaussianSplattingModel:
         if c.pose_lr_rot <= 0 and c.pose_lr_trans <= 0:
             self.pose_refiner = None
             return None
-        if getattr(self, "_graphs", None):
+        if self._graphs:
             raise ValueError("pose refinement (pose_lr_rot / pose_lr_trans) does not combine with capture_step_graphs: a "
                              "captured graph bakes the camera in")
         from .pose import PoseRefiner
@@ -307,15 +321,9 @@ class DepthGaussianSplattingModel:
         # the autograd / eval path has no replay logic: it always bins with a synchronous budget (a
         # sync-free training budget would turn an eval view that needs more pairs into background)
         budget = self.budget if self.budget.sync else self._sync_budget
-        stats = ()
-        if depth_stats:
-            rgb, depth_acc, alpha, radii, *stats = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
-                                                              self.tuned(cam, keep=False), deg, budget=budget,
-                                                              opts=self.tuning.raster_opts(), depth_stats=True)
-        else:
-            rgb, depth_acc, alpha, radii = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
-                                                      self.tuned(cam, keep=False), deg, budget=budget,
-                                                      opts=self.tuning.raster_opts())
+        rgb, depth_acc, alpha, radii, *stats = ops.render(p.means, p.log_scales, p.quats, p.opac_logit, p.sh,
+                                                          self.tuned(cam, keep=False), deg, budget=budget,
+                                                          opts=self.tuning.raster_opts(), depth_stats=depth_stats)
         depth = depth_acc / torch.clamp(alpha, min=1e-10)
         out = dict(rgb=rgb, depth=depth[..., None], accumulation=alpha[..., None],
                    depth_acc=depth_acc, alpha=alpha, radii=radii)
@@ -347,7 +355,6 @@ class DepthGaussianSplattingModel:
 
     def get_loss_dict(self, outputs, view: View) -> Dict[str, torch.Tensor]:
         c = self.config
-        H, W = view.rgb.shape[:2]
         rgb = outputs["rgb"]
         es = self.exposure_set
         if es is not None and es.owns(view) and self.step >= c.exposure_start_step and "rgb_raw" not in outputs:
@@ -474,6 +481,51 @@ class DepthGaussianSplattingModel:
                         uncertainty_weight=c.uncertainty_weight, eps=c.depth_eps)
         return spec
 
+    def _image_terms(self, view: View, cam: Camera, depth_acc, fT):
+        """Monocular depth, then the normal prior -> (their keys of ``last``: those of the terms that ran, v_depth, v_alpha)."""
+        c, ran = self.config, {}
+        v_depth = v_alpha = None
+        if self.mono_depth_local_active(view):   # global + patch-wise term in one op: the same two images
+            patch_off = ran["mono_patch_offset"] = self.patch_offset()
+            ran["mono_stats"], v_depth, v_alpha = ops.depth_corr_local_fwd_bwd(
+                depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min, weight_global=max(c.mono_depth_mult, 0.0),
+                weight_local=c.mono_depth_local_mult, patch_tiles=c.mono_depth_patch_tiles, offset=patch_off,
+                min_fill=c.mono_depth_patch_min_fill, min_var_ratio=c.mono_depth_patch_min_var)
+        elif self.mono_depth_active(view):
+            ran["mono_stats"], v_depth, v_alpha = ops.depth_corr_fwd_bwd(
+                depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min, weight=c.mono_depth_mult)
+        if self.normal_prior_active(view):   # after the Pearson op: the term adds to its two images
+            ran["normal_stats"], _, v_depth, v_alpha = ops.depth_normal_fwd_bwd(
+                cam, depth_acc, fT, view.normal_prior, view.normal_conf, c.normal_alpha_min, c.normal_max_jump,
+                weight=c.normal_prior_mult, accumulate_into=(v_depth, v_alpha) if "mono_stats" in ran else None)
+        return ran, v_depth, v_alpha
+
+    def _rgb_loss_backward(self, view: View, cam: Camera, lists, images, v_depth, v_alpha, exposure, guard, may_pipeline: bool):
+        """SSIM + K7, band-pipelined or in sequence (with the view's ``exposure`` row: SSIM on the compensated image) -> (partials,
+        tile_loss, ssim_sum, expo_out); ``lists`` = (splats, group_base, sorted_gid, tile_start), ``images`` = (rgb, depth_acc, final_T)."""
+        c, rgb = self.config, images[0]
+        w_ssim = -c.ssim_lambda / (3 * cam.H * cam.W)
+        spec = self.loss_spec(view)
+        if (exposure is None and c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles
+                and may_pipeline and not torch.cuda.is_current_stream_capturing()):
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(device=rgb.device)
+            return ops.rasterize_bwd_ssim_pipelined(cam, *lists, *images, view.rgb, w_ssim, spec, self._side_stream) + (None,)
+        ssim_sum = v_rgb = expo_out = None
+        img = rgb if exposure is None else ops.exposure_fwd(rgb, exposure)
+        if c.ssim_lambda > 0:
+            ssim_sum, v_rgb = ops.ssim_fwd_bwd(img, view.rgb, weight=w_ssim, reduce=False)
+        if exposure is not None:    # forms the L1 term on the compensated image, hands K7 its upstream image, steps the row
+            es = self.exposure_set
+            expo_out, v_rgb = ops.exposure_bwd(rgb, exposure, gt=view.rgb, l1_weight=spec["l1_weight"], v_img=v_rgb,
+                                               guard=guard, state=exposure, adam=es.adam,
+                                               out=(torch.empty(ops._lib.EXPO_OUT, dtype=torch.float32, device=rgb.device),
+                                                    es.scratch(cam.W, cam.H)))
+            spec.update(gt_rgb=None, l1_weight=0.0)     # the L1 term went in through v_rgb; the depth terms stay fused
+        partials, tile_loss = ops.rasterize_bwd(cam, *lists, *images, v_rgb=v_rgb, v_depth=v_depth, v_alpha=v_alpha,
+                                                loss=spec, want_tile_loss=True)
+        return partials, tile_loss, ssim_sum, expo_out
+
     def forward_backward(self, view: View, want_v_xy: bool = False, fuse_adam: bool = False,
                          color_block: Optional[torch.Tensor] = None, begin_step: bool = True,
                          colors=None, prefetch=None, next_front=None, pose_grad: bool = False,
@@ -486,71 +538,29 @@ class DepthGaussianSplattingModel:
         image C' = A rgb + b -- ``ops.exposure_fwd``, SSIM on C', ``ops.exposure_bwd`` (which forms the L1 term, hands K7
         its upstream image and steps the row), K7 without its fused L1 term -- and ``last["exposure"]`` = its [32] result.
         No host sync unless ``budget.sync``.  Returns device tensors (l1+depth tile losses, ssim sum)."""
-        p, c, cam = self.params, self.config, self.tuned(view.cam)
-        deg = self.active_sh_degree()
-        H, W = cam.H, cam.W
+        p, cam, deg = self.params, self.tuned(view.cam), self.active_sh_degree()
         splats, radii, group_base, tile_start, sorted_gid, status = ops.project_bin_sort(
             cam, p.means, p.log_scales, p.quats, p.opac_logit, p.sh, deg, self.budget, want_radii=want_v_xy,
             colors=colors, next_front=next_front)
         guard = None if self.budget.sync else status   # overflowed frame => optimizer kernels are no-ops
         rgb, depth_acc, fT, fidx = ops.rasterize_fwd(cam, splats, sorted_gid, tile_start, opts=self.tuning.raster_opts())
-        v_img, ssim_sum = None, None
-        mono_stats = v_depth = v_alpha = None
-        patch_off = None
-        if self.mono_depth_local_active(view):   # global + patch-wise term in one op: the same two images
-            patch_off = self.patch_offset()
-            mono_stats, v_depth, v_alpha = ops.depth_corr_local_fwd_bwd(
-                depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min, weight_global=max(c.mono_depth_mult, 0.0),
-                weight_local=c.mono_depth_local_mult, patch_tiles=c.mono_depth_patch_tiles, offset=patch_off,
-                min_fill=c.mono_depth_patch_min_fill, min_var_ratio=c.mono_depth_patch_min_var)
-        elif self.mono_depth_active(view):   # image-space term beside K7, which adds its fused terms on top of the two images
-            mono_stats, v_depth, v_alpha = ops.depth_corr_fwd_bwd(depth_acc, fT, view.mono_depth, c.mono_depth_alpha_min,
-                                                                  weight=c.mono_depth_mult)
-        normal_stats = None
-        if self.normal_prior_active(view):   # after the Pearson op, on the same stream: the term adds to its two images
-            normal_stats, _, v_depth, v_alpha = ops.depth_normal_fwd_bwd(
-                cam, depth_acc, fT, view.normal_prior, view.normal_conf, c.normal_alpha_min, c.normal_max_jump,
-                weight=c.normal_prior_mult, accumulate_into=None if mono_stats is None else (v_depth, v_alpha))
-        expo_out = None
-        if exposure is not None:
-            if color_block is not None:
-                raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps")
-            es = self.exposure_set
-            spec = self.loss_spec(view)
-            rgb_c = ops.exposure_fwd(rgb, exposure)
-            if c.ssim_lambda > 0:
-                ssim_sum, v_img = ops.ssim_fwd_bwd(rgb_c, view.rgb, weight=-c.ssim_lambda / (3 * H * W), reduce=False)
-            expo_out, v_rgb = ops.exposure_bwd(rgb, exposure, gt=view.rgb, l1_weight=spec["l1_weight"], v_img=v_img,
-                                               guard=guard, state=exposure, adam=es.adam,
-                                               out=(torch.empty(ops._lib.EXPO_OUT, dtype=torch.float32, device=rgb.device),
-                                                    es.scratch(W, H)))
-            spec.update(gt_rgb=None, l1_weight=0.0)     # the L1 term went in through v_rgb; the depth terms stay fused
-            partials, tile_loss = ops.rasterize_bwd(cam, splats, group_base, sorted_gid, tile_start, rgb,
-                                                    depth_acc, fT, v_rgb=v_rgb, v_depth=v_depth, v_alpha=v_alpha,
-                                                    loss=spec, want_tile_loss=True)
-        elif (c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles and mono_stats is None
-                and normal_stats is None and not torch.cuda.is_current_stream_capturing()):
-            if getattr(self, "_side_stream", None) is None:
-                self._side_stream = torch.cuda.Stream(device=rgb.device)
-            partials, tile_loss, ssim_sum = ops.rasterize_bwd_ssim_pipelined(
-                cam, splats, group_base, sorted_gid, tile_start, rgb, depth_acc, fT, view.rgb,
-                -c.ssim_lambda / (3 * H * W), self.loss_spec(view), self._side_stream)
-        else:
-            if c.ssim_lambda > 0:
-                ssim_sum, v_img = ops.ssim_fwd_bwd(rgb, view.rgb, weight=-c.ssim_lambda / (3 * H * W), reduce=False)
-            partials, tile_loss = ops.rasterize_bwd(cam, splats, group_base, sorted_gid, tile_start, rgb,
-                                                    depth_acc, fT, v_rgb=v_img, v_depth=v_depth, v_alpha=v_alpha,
-                                                    loss=self.loss_spec(view), want_tile_loss=True)
-        pose_out = None
+        ran, v_depth, v_alpha = self._image_terms(view, cam, depth_acc, fT)
+        if exposure is not None and color_block is not None:
+            raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps")
+        partials, tile_loss, ssim_sum, expo_out = self._rgb_loss_backward(
+            view, cam, (splats, group_base, sorted_gid, tile_start), (rgb, depth_acc, fT), v_depth, v_alpha, exposure, guard,
+            may_pipeline=not ran)
+        if expo_out is not None:
+            ran["exposure"] = expo_out
         if pose_grad:
             if color_block is not None:
                 raise ValueError("pose refinement (pose_lr_rot / pose_lr_trans) is not supported in data-parallel steps")
             G = ops._lib.load().tgs_num_groups(p.N)
             if self._pose_scratch is None or self._pose_scratch.shape[0] < G or self._pose_scratch.device != p.flat.device:
                 self._pose_scratch = torch.empty(max(G, 1), ops._lib.POSE_ROW, dtype=torch.float32, device=p.flat.device)
-            pose_out = ops.pose_grad(cam, p.means, p.log_scales, p.quats, p.sh, deg, splats, group_base, partials,
-                                     guard=guard, out=(torch.empty(ops._lib.POSE_OUT, dtype=torch.float32, device=p.flat.device),
-                                                       self._pose_scratch))
+            ran["pose_grad"] = ops.pose_grad(cam, p.means, p.log_scales, p.quats, p.sh, deg, splats, group_base, partials,
+                                            guard=guard, out=(torch.empty(ops._lib.POSE_OUT, dtype=torch.float32, device=p.flat.device),
+                                                              self._pose_scratch))
         if fuse_adam:
             v_xy = self.optimizer.backward_and_step(cam, deg, splats, group_base, partials, want_v_xy,
                                                     begin=begin_step, guard=guard, prefetch=prefetch)
@@ -560,9 +570,7 @@ class DepthGaussianSplattingModel:
                 rows, blocks = color_block
                 v_xy = torch.empty(p.N, 2, dtype=torch.float32, device=p.flat.device) if want_v_xy else None
                 out4 = p.grad_views()[:4]
-
-                def backward_chunk(c, cam=cam, deg=deg, splats=splats, group_base=group_base, partials=partials,
-                                   guard=guard, v_xy=v_xy):
+                def backward_chunk(c):
                     ops.project_bwd_color(cam, p.means, p.log_scales, p.quats, p.opac_logit, p.sh, deg, splats,
                                           group_base, partials, out4, blocks[c], guard=guard, rows=rows[c], v_xy=v_xy)
                 self._backward_chunk = backward_chunk
@@ -574,17 +582,7 @@ class DepthGaussianSplattingModel:
             v_xy = ops.project_bwd(cam, p.means, p.log_scales, p.quats, p.opac_logit, p.sh, deg, splats,
                                    group_base, partials, out=p.grad_views(), want_v_xy=want_v_xy, guard=guard)[5]
         self.last = dict(rgb=rgb, depth_acc=depth_acc, final_T=fT, splats=splats, v_xy=v_xy, radii=radii,
-                         tile_loss=tile_loss, ssim_sum=ssim_sum, status=status, guard=guard, view=view)
-        if pose_out is not None:
-            self.last["pose_grad"] = pose_out
-        if expo_out is not None:
-            self.last["exposure"] = expo_out
-        if mono_stats is not None:
-            self.last["mono_stats"] = mono_stats
-        if patch_off is not None:
-            self.last["mono_patch_offset"] = patch_off
-        if normal_stats is not None:
-            self.last["normal_stats"] = normal_stats
+                         tile_loss=tile_loss, ssim_sum=ssim_sum, status=status, guard=guard, view=view, **ran)
         return tile_loss, ssim_sum
 
     def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None, exposure=None) -> Dict[str, torch.Tensor]:
@@ -627,7 +625,7 @@ class DepthGaussianSplattingModel:
         # the last frame's tile count per Gaussian (the packed rect of its record): Gaussians with LONG runs of tiles are
         # dealt evenly over the binning groups instead of sitting next to their spatial neighbours (optim.balanced_order)
         hits = None
-        cams = list(getattr(self, "_recent_cams", {}).values()) if self.config.balance_long_runs else []
+        cams = list(self._recent_cams.values()) if self.config.balance_long_runs else []
         if os.environ.get("TGS_BALANCE_LONG_RUNS", "1") == "0":     # A/B switch
             cams = []
         if cams:
@@ -639,8 +637,7 @@ class DepthGaussianSplattingModel:
                 sp = ops.project_fwd(cam, p.means, p.log_scales, p.quats, p.opac_logit, None, -1)
                 rect = sp[:, 10].contiguous().view(torch.int32)
                 hits = hits + ((rect >> 16) & 255) * ((rect >> 24) & 255)
-            dp = getattr(self, "_dp", None)
-            if dp is not None and dp.active:
+            if self._dp is not None and self._dp.active:
                 # data parallel: every rank has seen ITS views only, and the replicas must agree on the row order -- sum the
                 # counts over the ranks (the same collective on every rank: re-sorts happen at refinements, which are
                 # barrier points) and divide by the rank-independent total
@@ -670,7 +667,7 @@ class DepthGaussianSplattingModel:
         long_run = self.tuning.long_run or 32     # (0 only while hits is None: plain Morton order, the value is not read)
         perm = balanced_order(self.params.means, hits, long_run=long_run)
         self.params.permute_(perm, self.optimizer.exp_avg, self.optimizer.exp_avg_sq)
-        density = getattr(self, "density", None)
+        density = self.density
         if density is not None:
             density.grad_norm_sum = density.grad_norm_sum[perm]
             density.vis_count = density.vis_count[perm]
@@ -703,11 +700,8 @@ class DepthGaussianSplattingModel:
         buffers, rewinds its step counters and replays the affected views -- the model ends up exactly
         where the synchronous budget would have put it (tests/test_gpu_api_surfaces.py)."""
         self.budget = ops.IntersectBudget(capacity=capacity, sync=False, speculative=True)
-        self._pending = collections.deque()
-        self._max_in_flight = max_in_flight
-        self._pinned = []
-        self._dp_status = None      # device {0, any rank overflowed} of the last data-parallel step
-        self._dp = None
+        self._pending, self._max_in_flight, self._pinned = collections.deque(), max_in_flight, []
+        self._dp = self._dp_status = None
         # longest tile list the settled frames have shown (status[3]) -> the budget's max_list_hint: after LIST_HINT_AFTER
         # good frames the sort launches for list classes beyond 1.5 x that are no longer issued (two near-empty launches,
         # ~9 us per step at cfg3); a frame that breaks the bound is void and replayed like an overflow, with the hint off
@@ -745,14 +739,13 @@ class DepthGaussianSplattingModel:
                 self._dp.peer.raise_if(int(host[6]))
             if int(host[5] if self._dp is not None else host[1]) == 0:
                 self._pending.popleft()
-                self._seen_need = max(getattr(self, "_seen_need", 0), int(host[2]), int(host[0]))
+                self._seen_need = max(self._seen_need, int(host[2]), int(host[0]))
                 self._seen_longest = max(self._seen_longest, int(host[3]))
                 self._good_frames += 1
                 # armed once every training view of the current resolution level can have been seen (with more
                 # than 16 views the bound came from a subset, and a later view beyond 1.5 x + 64 voided its frame)
-                dens = getattr(self, "density", None)
-                need_frames = max(self.LIST_HINT_AFTER, dens.cfg.num_train_data if dens is not None else 0,
-                                  len(getattr(self, "_recent_cams", ())))
+                need_frames = max(self.LIST_HINT_AFTER, len(self._recent_cams),
+                                  self.density.cfg.num_train_data if self.density is not None else 0)
                 if self.list_hint and self._good_frames >= need_frames:
                     self.budget.max_list_hint = max(self.budget.max_list_hint, int(1.5 * self._seen_longest) + 64)
                 self._pinned.append(host)
@@ -772,7 +765,7 @@ class DepthGaussianSplattingModel:
             self._prefetch_ready = None     # announced by a voided step: its front buffers were cleared under the sticky word
             self.optimizer.t -= len(redo)
             self.step -= len(redo)
-            self.speculative_replays = getattr(self, "speculative_replays", 0) + len(redo)
+            self.speculative_replays += len(redo)
             for v, h, _ in redo:
                 self._pinned.append(h)
                 self.train_step(v, self._dp)
@@ -780,7 +773,7 @@ class DepthGaussianSplattingModel:
     def flush(self) -> None:
         """Wait for every enqueued step and settle pending overflow checks (call before reading
         ``last``, saving a checkpoint or evaluating when the speculative budget is on)."""
-        if getattr(self, "_pending", None) is not None and self.budget.speculative:
+        if self._pending is not None and self.budget.speculative:
             self._speculative_poll(drain=True)
         if self.pose_refiner is not None:
             self.pose_refiner.flush(self)
@@ -837,7 +830,55 @@ class DepthGaussianSplattingModel:
         prefetch; same results bit for bit).  The caller promises not to modify the parameters
         between the two calls except through this class."""
         distributed = dp is not None and dp.active
-        opt = self.optimizer
+        opt, density = self.optimizer, self.density
+        pose_on, expo_row, next_view = self._begin_refiners(view, next_view, distributed)
+        full_view = view    # what the speculative budget replays (the schedule is applied again on the replay)
+        view, next_view = self._apply_schedule(view, next_view)
+        deg = self.active_sh_degree()
+        pre, self._prefetch_ready = self._prefetch_ready, None
+        if self._graphs and not distributed and density is None and self._replay_graph(view, deg):
+            return
+        fuse = (not distributed) and self.fuse_adam and opt.can_fuse_with_backward(deg)
+        factored = distributed and self.dp_factored_sh and opt.can_gather_sh()
+        if self.budget.speculative and distributed and not factored:
+            raise RuntimeError("the speculative intersection budget does not combine with the dense (flat all-reduce) "
+                               "data-parallel exchange")
+        self._dp = dp if distributed else None
+        block = self._exchange_buffers(dp) if factored else None
+        # prefetched by the previous step: colours (+ front) from the fused optimizer kernel, or the front alone from
+        # the geometry Adam of a data-parallel step
+        colors = pre if (pre is not None and (fuse or (factored and pre.front_issued and not pre.colors_valid))
+                         and pre.matches(self.tuned(view.cam), self.params.N, deg)) else None
+        arm = self._arm_prefetch(next_view, deg, fuse, factored, in_use=colors if fuse else pre)
+        self.forward_backward(view, want_v_xy=density is not None, fuse_adam=fuse, color_block=block,
+                              colors=colors, prefetch=arm if fuse else None,
+                              next_front=arm.front if arm is not None else None, pose_grad=pose_on, exposure=expo_row)
+        self._prefetch_ready = arm
+        if pose_on:     # taken at the (possibly downscaled) camera, applied to the full-resolution view's pose
+            self.pose_refiner.submit(full_view, self.last["pose_grad"])
+        if density is not None and not factored:
+            # a frame that overflowed its intersection buffer (sync-free budget) rendered nothing and will be
+            # replayed: it must not count as a view (guard = its status word, evaluated on the device)
+            density.accumulate(self.last["v_xy"], self.last["radii"], view.cam.W, view.cam.H, guard=self.last["guard"],
+                               view_key=id(full_view))
+        if factored:
+            self._factored_tail(dp, view, deg, arm)
+        elif distributed:
+            dp.reduce_and_step(self.params.grad, opt.step_range, opt.begin_step)
+        elif not fuse:
+            opt.step(guard=self.last["guard"])
+        self.step += 1
+        if self.budget.speculative:
+            self._speculative_track(full_view, distributed)
+        elif self.budget.sync and distributed and getattr(dp, "peer", None) is not None:
+            # synchronous budget: no guard words exist, so the error word is read every step (this mode syncs per step anyway).  A pre-sized
+            # sync-free budget (bench.py) neither syncs nor polls: its caller checks the transport at its own sync point (GradSync.check_transport)
+            dp.peer.raise_if(int(dp.peer.err_word.item()))
+        if density is not None and density.due(self.step) and self._refined_at != self.step:
+            self._refine(dp)
+
+    def _begin_refiners(self, view: View, next_view: Optional[View], distributed: bool):
+        """Checks and pending updates of the pose refiner and the exposure set -> (pose_on, expo_row or None, next_view or None)."""
         ref, pose_on = self.pose_refiner, False
         if ref is None and (self.config.pose_lr_rot > 0 or self.config.pose_lr_trans > 0):
             raise ValueError("pose_lr_rot / pose_lr_trans are set but no view is registered for refinement: call "
@@ -862,18 +903,21 @@ class DepthGaussianSplattingModel:
                 raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps (dp.active)")
             if es.owns(view) and self.step >= self.config.exposure_start_step:
                 expo_row = es.row(view)     # of the full-resolution view: its downscaled forms step the same row
+        return pose_on, expo_row, next_view
+
+    def _apply_schedule(self, view: View, next_view: Optional[View]):
+        """The recent cameras, the learning rate of the means, the coarse-to-fine level -> (view, next_view) at their levels."""
         if self.config.balance_long_runs and self.config.spatial_sort:
             # the cameras of the last steps (full resolution), for the next spatial_sort (host-side bookkeeping only)
-            rc = self.__dict__.setdefault("_recent_cams", collections.OrderedDict())
+            rc = self._recent_cams
             rc[id(view.cam)] = view.cam
             rc.move_to_end(id(view.cam))
             if len(rc) > 16:
                 rc.popitem(last=False)
-        opt.lrs["means"] = self.config.lr_means_at(self.step)   # scheduled position learning rate
-        full_view = view    # what the speculative budget replays (the schedule is applied again on the replay)
+        self.optimizer.lrs["means"] = self.config.lr_means_at(self.step)   # scheduled position learning rate
         if self.config.num_downscales > 0:   # coarse-to-fine: this step (and the announced next one) at their resolutions
             d = self.config.downscale_factor(self.step)
-            if d != getattr(self, "_last_downscale", d) and getattr(self, "_pending", None) is not None:
+            if self._last_downscale not in (None, d) and self._pending is not None:
                 # a new resolution level: the lists get ~4x longer -- learn the list bound again instead of voiding a frame
                 self._seen_longest, self._good_frames = 0, 0
                 self.budget.max_list_hint = -1
@@ -881,170 +925,123 @@ class DepthGaussianSplattingModel:
             view = view.downscaled(d)
             if next_view is not None:
                 next_view = next_view.downscaled(self.config.downscale_factor(self.step + 1))
-        deg = self.active_sh_degree()
-        pre, self._prefetch_ready = getattr(self, "_prefetch_ready", None), None
-        graphs = getattr(self, "_graphs", None)
-        if graphs and not distributed and getattr(self, "density", None) is None:
-            entry = graphs.get(id(view))
-            if entry is not None and entry[2] == deg and entry[3] == self.params.N:
-                opt.begin_step()
-                opt.upload_bias_corr()
-                entry[0].replay()
-                self.last = entry[1]
-                self.step += 1
-                return
-            if entry is not None:
-                self.drop_step_graphs()
-        fuse = (not distributed) and self.fuse_adam and opt.can_fuse_with_backward(deg)
-        factored = distributed and self.dp_factored_sh and opt.can_gather_sh()
-        density = getattr(self, "density", None)
-        if self.budget.speculative and distributed and not factored:
-            raise RuntimeError("the speculative intersection budget does not combine with the dense (flat all-reduce) "
-                               "data-parallel exchange")
-        self._dp = dp if distributed else None
-        block = None
-        if factored:
-            # the rank's colour-gradient blocks, one per row chunk of the pipelined exchange: [3 rows + 4] each
-            # (colour gradients | camera position | overflow flag), and their all-gathered images [world, 3 rows + 4]
-            rows = dp.color_chunk_rows(self.params.N)
-            n = 3 * self.params.N + 4 * len(rows)
-            if (self._color_block is None or self._color_block.numel() != n or self._color_all.numel() != n * dp.world
-                    or self._color_rows != rows):
-                dev = self.params.flat.device
-                self._color_block = torch.zeros(n, dtype=torch.float32, device=dev)
-                self._color_all = torch.zeros(dp.world * n, dtype=torch.float32, device=dev)
-                self._color_rows, self._color_blocks, self._color_blocks_all, off = rows, [], [], 0
-                for b, e in rows:
-                    m = 3 * (e - b) + 4
-                    self._color_blocks.append(self._color_block[off:off + m])
-                    self._color_blocks_all.append(self._color_all[dp.world * off:dp.world * (off + m)].view(dp.world, m))
-                    off += m
-            block = (rows, self._color_blocks)
-        # prefetched by the previous step: colours (+ front) from the fused optimizer kernel, or the front alone from
-        # the geometry Adam of a data-parallel step
-        colors = pre if (pre is not None and (fuse or (factored and pre.front_issued and not pre.colors_valid))
-                         and pre.matches(self.tuned(view.cam), self.params.N, deg)) else None
-        arm = None
-        # the next view's K1 runs inside this step's optimizer kernel: under the rule its own step will run K8 with
-        next_cam = self.tuned(next_view.cam) if next_view is not None else None
-        if fuse and next_view is not None and self.active_sh_degree(self.step + 1) == deg:
-            bufs = getattr(self, "_prefetch_bufs", None)
-            N, dev = self.params.N, self.params.flat.device
-            if bufs is None or bufs[0].N != N or bufs[0].colors.device != dev:
-                bufs = self._prefetch_bufs = [ops.ColorPrefetch(N, dev), ops.ColorPrefetch(N, dev)]
-            # two buffers alternate: the one this step's K1 reads is not the one this step's K9 writes
-            # front prefetch: the optimizer kernel also runs the next view's K1 into that frame's buffers
-            front = None
-            if self.front_prefetch and not torch.cuda.is_current_stream_capturing():
-                front = ops.FrontBuffers(next_cam, N, self.budget.initial(N), density is not None, dev)
-            arm = (bufs[1] if colors is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget)
-        if (factored and next_view is not None and self.front_prefetch
-                and self.active_sh_degree(self.step + 1) == deg):
-            # data-parallel form of the front prefetch: the geometry Adam (last kernel of the step) also runs this
-            # rank's next K1; no colours (the SH rows are stepped by another kernel)
-            N, dev = self.params.N, self.params.flat.device
-            bufs = getattr(self, "_prefetch_bufs", None)
-            if bufs is None or bufs[0].N != N or bufs[0].colors.device != dev:
-                bufs = self._prefetch_bufs = [ops.ColorPrefetch(N, dev), ops.ColorPrefetch(N, dev)]
-            front = ops.FrontBuffers(next_cam, N, self.budget.initial(N), density is not None, dev)
-            arm = (bufs[1] if pre is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget, colors_valid=False)
-        self.forward_backward(view, want_v_xy=density is not None, fuse_adam=fuse, color_block=block,
-                              colors=colors, prefetch=arm if fuse else None,
-                              next_front=arm.front if arm is not None else None, pose_grad=pose_on, exposure=expo_row)
-        self._prefetch_ready = arm
-        if pose_on:     # taken at the (possibly downscaled) camera, applied to the full-resolution view's pose
-            ref.submit(full_view, self.last["pose_grad"])
-        if density is not None and not factored:
-            # a frame that overflowed its intersection buffer (sync-free budget) rendered nothing and will be
-            # replayed: it must not count as a view (guard = its status word, evaluated on the device)
-            density.accumulate(self.last["v_xy"], self.last["radii"], view.cam.W, view.cam.H, guard=self.last["guard"],
-                               view_key=id(full_view))
-        if factored:
-            dguard = None
-            if self.budget.speculative:   # agree the overflow verdict across ranks before anything touches the model
-                if self._dp_status is None:
-                    self._dp_status = torch.zeros(2, dtype=torch.int32, device=self.params.flat.device)
-                # a peer-exchange wait that times out raises both words: this step and every later one are voided.  Set every
-                # step: a refinement replaces the budget, and with it the sticky word the transport would otherwise keep pointing at
-                dp.set_poison_words(self.budget.sticky_word(self.params.flat.device), self._dp_status)
-                dguard = self._dp_status
+        return view, next_view
 
-            rows = self._color_rows
-
-            # the whole tail (SH Adam of every chunk + geometry Adam + the next view's K1) as ONE launch behind the
-            # geometry all-reduce, where that is a gain (GradSync.fused_tail: by world size -- on a node the chunked SH
-            # Adam hides under the transfers, which the fused launch cannot)
-            fused_tail = (arm is not None and not fuse and len(rows) <= 8 and opt.p.K >= 4 and self.params.N > 0 and dp.fused_tail())
-
-            def step_sh_chunk(c, allc, scale):
-                if c == 0 and dguard is not None:   # every chunk block of a rank carries the frame's flag
-                    ops.dp_agree_overflow(dp.world, rows[0][1] - rows[0][0], allc, dguard, self.budget.sticky)
-                if not fused_tail:
-                    opt.step_sh_gathered(dp.world, deg, allc, scale, guard=dguard, rows=rows[c])
-
-            if fused_tail:
-                step_geom = lambda b, e, scale: opt.step_sh_gathered_geom_and_project_next(
-                    dp.world, deg, rows, self._color_blocks_all, scale, dguard, arm)
-            elif arm is not None and not fuse:
-                step_geom = lambda b, e, scale: opt.step_geom_and_project_next(deg, scale, dguard, arm)
-            else:
-                step_geom = lambda b, e, scale: opt.step_range(b, e, scale, guard=dguard)
-            dp.pipelined_color_exchange_and_step(
-                self.params.grad[:opt.geom_end()], self._color_blocks, self._color_blocks_all, self._backward_chunk,
-                step_sh_chunk, step_geom, opt.begin_step)
-            self._backward_chunk = None
-            if density is not None:   # v_xy exists once the K8 chunks are enqueued
-                # guarded by the AGREED verdict (written by chunk 0's dp_agree_overflow, enqueued above), not by this
-                # rank's own status word: if another rank's frame overflowed, the step is voided on every rank and
-                # replayed, and this rank's (valid) frame must not be counted twice
-                # (data parallel: every rank sees its own views; the statistics are summed over the ranks at the
-                # refinement, the identities are not -- the window counts as complete by its length, as for anonymous views)
-                density.accumulate(self.last["v_xy"], self.last["radii"], view.cam.W, view.cam.H,
-                                   guard=dguard if dguard is not None else self.last["guard"])
-        elif distributed:
-            dp.reduce_and_step(self.params.grad, self.optimizer.step_range, self.optimizer.begin_step)
-        elif not fuse:
-            self.optimizer.step(guard=self.last["guard"])
+    def _replay_graph(self, view: View, deg: int) -> bool:
+        """Replay the graph captured for ``view`` -> True = the step is done.  A stale graph (SH degree, N) drops them all."""
+        entry = self._graphs.get(id(view))
+        if entry is None:
+            return False
+        if entry[2] != deg or entry[3] != self.params.N:
+            self.drop_step_graphs()
+            return False
+        self.optimizer.begin_step()
+        self.optimizer.upload_bias_corr()
+        entry[0].replay()
+        self.last = entry[1]
         self.step += 1
+        return True
+
+    def _exchange_buffers(self, dp):
+        """-> (rows, blocks) of the factored exchange: the rank's colour-gradient blocks, one per row chunk, [3 rows + 4] each
+        (colour gradients | camera position | overflow flag); ``_color_blocks_all``: their images [world, 3 rows + 4]."""
+        rows = dp.color_chunk_rows(self.params.N)
+        n = 3 * self.params.N + 4 * len(rows)
+        if (self._color_block is None or self._color_block.numel() != n or self._color_all.numel() != n * dp.world
+                or self._color_rows != rows):
+            dev = self.params.flat.device
+            self._color_block = torch.zeros(n, dtype=torch.float32, device=dev)
+            self._color_all = torch.zeros(dp.world * n, dtype=torch.float32, device=dev)
+            self._color_rows, self._color_blocks, self._color_blocks_all, off = rows, [], [], 0
+            for b, e in rows:
+                m = 3 * (e - b) + 4
+                self._color_blocks.append(self._color_block[off:off + m])
+                self._color_blocks_all.append(self._color_all[dp.world * off:dp.world * (off + m)].view(dp.world, m))
+                off += m
+        return rows, self._color_blocks
+
+    def _arm_prefetch(self, next_view: Optional[View], deg: int, fuse: bool, factored: bool, in_use):
+        """-> the ColorPrefetch armed for the next view (its K1 runs inside this step's last optimizer kernel, under the rule its own step
+        will run K8 with) or None.  Fused: colours + front; factored data parallel: the front alone.  Never the buffer ``in_use``."""
+        if next_view is None or not (fuse or (factored and self.front_prefetch)) or self.active_sh_degree(self.step + 1) != deg:
+            return None
+        next_cam = self.tuned(next_view.cam)
+        N, dev, bufs = self.params.N, self.params.flat.device, self._prefetch_bufs
+        if bufs is None or bufs[0].N != N or bufs[0].colors.device != dev:
+            bufs = self._prefetch_bufs = [ops.ColorPrefetch(N, dev), ops.ColorPrefetch(N, dev)]
+        front = None
+        if self.front_prefetch and not (fuse and torch.cuda.is_current_stream_capturing()):
+            front = ops.FrontBuffers(next_cam, N, self.budget.initial(N), self.density is not None, dev)
+        return (bufs[1] if in_use is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget, colors_valid=fuse)
+
+    def _factored_tail(self, dp, view: View, deg: int, arm) -> None:
+        """Factored data-parallel step after K7: agreed verdict, pipelined exchange with K8 and the Adam forms, statistics."""
+        opt, density, rows, dguard = self.optimizer, self.density, self._color_rows, None
+        if self.budget.speculative:   # agree the overflow verdict across ranks before anything touches the model
+            if self._dp_status is None:
+                self._dp_status = torch.zeros(2, dtype=torch.int32, device=self.params.flat.device)
+            # a peer-exchange wait that times out raises both words: this step and every later one are voided.  Set every
+            # step: a refinement replaces the budget, and with it the sticky word the transport would otherwise keep pointing at
+            dp.set_poison_words(self.budget.sticky_word(self.params.flat.device), self._dp_status)
+            dguard = self._dp_status
+        # the whole tail (SH Adam of every chunk + geometry Adam + the next view's K1) as ONE launch behind the
+        # geometry all-reduce, where that is a gain (GradSync.fused_tail: by world size -- on a node the chunked SH
+        # Adam hides under the transfers, which the fused launch cannot)
+        fused_tail = arm is not None and len(rows) <= 8 and opt.p.K >= 4 and self.params.N > 0 and dp.fused_tail()
+        def step_sh_chunk(c, allc, scale):
+            if c == 0 and dguard is not None:   # every chunk block of a rank carries the frame's flag
+                ops.dp_agree_overflow(dp.world, rows[0][1] - rows[0][0], allc, dguard, self.budget.sticky)
+            if not fused_tail:
+                opt.step_sh_gathered(dp.world, deg, allc, scale, guard=dguard, rows=rows[c])
+
+        if fused_tail:
+            step_geom = lambda b, e, scale: opt.step_sh_gathered_geom_and_project_next(
+                dp.world, deg, rows, self._color_blocks_all, scale, dguard, arm)
+        elif arm is not None:
+            step_geom = lambda b, e, scale: opt.step_geom_and_project_next(deg, scale, dguard, arm)
+        else:
+            step_geom = lambda b, e, scale: opt.step_range(b, e, scale, guard=dguard)
+        dp.pipelined_color_exchange_and_step(
+            self.params.grad[:opt.geom_end()], self._color_blocks, self._color_blocks_all, self._backward_chunk,
+            step_sh_chunk, step_geom, opt.begin_step)
+        self._backward_chunk = None
+        if density is not None:   # v_xy exists once the K8 chunks are enqueued
+            # guarded by the AGREED verdict (written by chunk 0's dp_agree_overflow, enqueued above), not by this
+            # rank's own status word: if another rank's frame overflowed, the step is voided on every rank and
+            # replayed, and this rank's (valid) frame must not be counted twice (ADVICE r3)
+            # (data parallel: every rank sees its own views; the statistics are summed over the ranks at the
+            # refinement, the identities are not -- the window counts as complete by its length, as for anonymous views)
+            density.accumulate(self.last["v_xy"], self.last["radii"], view.cam.W, view.cam.H,
+                               guard=dguard if dguard is not None else self.last["guard"])
+
+    def _refine(self, dp) -> None:
+        """The refinement that is due, a budget for the new N; what was built for the old rows goes; the re-sort counter."""
         if self.budget.speculative:
-            self._speculative_track(full_view, distributed)
-        elif self.budget.sync and distributed and getattr(dp, "peer", None) is not None:
-            # synchronous budget: no guard words exist, so the error word is read every step (this mode syncs per step
-            # anyway).  A pre-sized sync-free budget (bench.py) neither syncs nor polls: its caller checks the transport
-            # at its own sync point (GradSync.check_transport), as it checks the budget.
-            dp.peer.raise_if(int(dp.peer.err_word.item()))
-        if density is not None and density.due(self.step) and getattr(self, "_refined_at", None) != self.step:
-            if self.budget.speculative:
-                # barrier: settle every pending overflow verdict first (a drain that finds one replays the
-                # affected steps -- possibly including this one, whose replay then refines; `_refined_at`
-                # keeps the outer call from refining a second time)
-                self.flush()
-                if getattr(self, "_refined_at", None) == self.step:
-                    return
-            n_before = self.params.N
-            self.params, self.optimizer, self.last_refine = density.refine(self.params, self.optimizer, self.step, dp)
-            self._refined_at = self.step
-            if self.budget.speculative:
-                # the intersection count follows N: size the new buffers from the largest capacity any frame since
-                # the last refinement needed (the verdicts just drained carry it), scaled by the growth of N, +25 %;
-                # a wrong guess only costs a replay.  (Never from the old capacity: that would compound.)
-                seen = getattr(self, "_seen_need", 0)
-                ratio = max(1.0, self.params.N / max(n_before, 1))
-                cap = int(seen * ratio * 1.25) + 4096 if seen > 0 else int(self.budget.capacity * ratio) + 4096
-                self._seen_need = 0
-                self._seen_longest, self._good_frames = 0, 0     # the lists change with the Gaussians: learn the bound again
-                self.budget = ops.IntersectBudget(capacity=cap, sync=False, speculative=True)
-            else:
-                self.budget = ops.IntersectBudget()  # the intersection count changes with N
-            self._prefetch_ready = None
-            self._graphs = {}
-            if self.config.spatial_sort:
-                # refine() puts every spawned row directly behind its parent, so the buffer stays spatially
-                # ordered; the full re-sort (argsort + gathers of parameters and both moment buffers) only
-                # corrects the slow drift of the means, every `resort_every_refines` refinements
-                self._refines_since_sort = getattr(self, "_refines_since_sort", 0) + 1
-                if self._refines_since_sort >= self.config.resort_every_refines:
-                    self.spatial_sort()
+            # barrier: settle every pending overflow verdict first (a drain that finds one replays the
+            # affected steps -- possibly including this one, whose replay then refines; `_refined_at`
+            # keeps the outer call from refining a second time)
+            self.flush()
+            if self._refined_at == self.step:
+                return
+        n_before = self.params.N
+        self.params, self.optimizer, self.last_refine = self.density.refine(self.params, self.optimizer, self.step, dp)
+        self._refined_at = self.step
+        if self.budget.speculative:
+            # the intersection count follows N (capacity_after_refine); a wrong guess only costs a replay
+            cap = ops.capacity_after_refine(self._seen_need, self.budget.capacity, n_before, self.params.N)
+            self._seen_need = self._seen_longest = self._good_frames = 0     # the lists change with the Gaussians: learn the bound again
+            self.budget = ops.IntersectBudget(capacity=cap, sync=False, speculative=True)
+        else:
+            self.budget = ops.IntersectBudget()  # the intersection count changes with N
+        self._prefetch_ready = None
+        self._graphs = {}
+        if self.config.spatial_sort:
+            # refine() puts every spawned row directly behind its parent, so the buffer stays spatially
+            # ordered; the full re-sort (argsort + gathers of parameters and both moment buffers) only
+            # corrects the slow drift of the means, every `resort_every_refines` refinements
+            self._refines_since_sort += 1
+            if self._refines_since_sort >= self.config.resort_every_refines:
+                self.spatial_sort()
 
     # -- checkpoint -----------------------------------------------------------------------------
     def state_dict(self):
@@ -1069,7 +1066,7 @@ class DepthGaussianSplattingModel:
             self.budget = ops.IntersectBudget()
             self._color_block = self._color_all = None
             self._graphs = {}
-            if getattr(self, "density", None) is not None:
+            if self.density is not None:
                 self.density.reset_stats(sd["N"], dev)
         self.params.flat.copy_(sd["flat"])
         self._prefetch_ready = None

@@ -129,6 +129,14 @@ class IntersectBudget:
 _default_budget = IntersectBudget()
 
 
+def capacity_after_refine(seen: int, old_capacity: int, n_before: int, n_after: int) -> int:
+    """Capacity of a speculative budget after a refinement took N from ``n_before`` to ``n_after``: the largest capacity any
+    frame since the last refinement needed (``seen``) x the growth of N (at least 1) + 25 % + 4096; nothing seen: the old
+    capacity x that growth + 4096 (only then: from the old capacity every time, it would compound)."""
+    ratio = max(1.0, n_after / max(n_before, 1))
+    return int(seen * ratio * 1.25) + 4096 if seen > 0 else int(old_capacity * ratio) + 4096
+
+
 # ------------------------------------------------------------------------------------------------
 # thin wrappers (one per C entry point)
 # ------------------------------------------------------------------------------------------------
@@ -152,38 +160,14 @@ def bin_sort(cam: Camera, splats, budget: Optional[IntersectBudget] = None):
     lib = _lib.load()
     budget = budget or _default_budget
     N = splats.shape[0]
-    dev = splats.device
-    T = cam.num_tiles
-    G = lib.tgs_num_groups(N)
     cs = cam.c_struct()
-    group_base = torch.empty(max(G, 1), dtype=torch.int32, device=dev)
-    tile_start = torch.empty(T + 1 + 512, dtype=torch.int32, device=dev)[:T + 1]   # + 512 scratch ints of the rasterizer (tgs.h)
-    nc = lib.tgs_tile_counter_len(cam.W, cam.H)
-    counters = torch.empty(nc + 4, dtype=torch.int32, device=dev)   # per-XCD tile counters + sub-list starts | status[4]
-    tile_cursor, status, status4 = counters[:nc], counters[nc:nc + 2], counters[nc:]
-    # block -> tile schedule of K6 / K7 (tiles dealt to the XCDs in granules of 8, longest list first inside each XCD); it rides on the
-    # tile_start tensor object so that the (tile_start, sorted_gid) pair keeps its meaning for callers
-    tile_order = torch.empty(lib.tgs_tile_order_len(cam.W, cam.H), dtype=torch.int32, device=dev)
-    tile_start.tile_order = tile_order
-    tile_start.slot_ok = None          # quadrant bitmaps K6 leaves for K7 (rasterize_fwd allocates and fills them)
-    cap = budget.initial(N)
+    fb = FrontBuffers(cam, N, budget.initial(N), False, splats.device, records=False)
     while True:
-        sorted_gid = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        scratch = torch.empty(lib.tgs_sort_scratch_bytes(cap), dtype=torch.uint8, device=dev)
-        check(lib.tgs_bin_sort(C.byref(cs), N, ptr(splats), ptr(group_base), ptr(tile_start), _tile_start_len(tile_start),
-                               ptr(tile_cursor), ptr(sorted_gid), ptr(tile_order), cap, ptr(scratch),
-                               ptr(status), ptr(budget.sticky_word(dev)), budget.list_hint(), _stream()), "tgs_bin_sort")
-        budget.last_status = status
-        budget.last_status4 = status4
-        if not budget.sync:
-            break
-        n, ovf, need, budget.last_longest = status4.tolist()
-        budget.last_n, budget.last_need = n, max(n, need)
-        if not ovf:
-            break
-        cap = int(n * budget.growth) + 1024
-        budget.capacity = cap
-    return group_base, tile_start, sorted_gid, status
+        check(lib.tgs_bin_sort(C.byref(cs), N, ptr(splats), ptr(fb.group_base), ptr(fb.tile_start), _tile_start_len(fb.tile_start),
+                               ptr(fb.tile_cursor), ptr(fb.sorted_gid), ptr(fb.tile_start.tile_order), fb.cap, ptr(fb.scratch),
+                               ptr(fb.status), ptr(budget.sticky_word(splats.device)), budget.list_hint(), _stream()), "tgs_bin_sort")
+        if not fb.settle(budget):
+            return fb.group_base, fb.tile_start, fb.sorted_gid, fb.status
 
 
 class ColorPrefetch:
@@ -224,11 +208,12 @@ class FrontBuffers:
     tgs_project_bwd_adam_next_front): records, group bases, per-tile counters and ranks are then filled by that
     kernel, and project_bin_sort only scans, fills and sorts (tgs_project_bin_sort_front)."""
 
-    def __init__(self, cam: Camera, N: int, cap: int, want_radii: bool, dev):
+    def __init__(self, cam: Camera, N: int, cap: int, want_radii: bool, dev, records: bool = True):
         lib = _lib.load()
         T = cam.num_tiles
-        self.N, self.cap, self.cam = N, cap, cam
-        self.splats = torch.empty(max(N, 1), SPLAT_FLOATS, dtype=torch.float32, device=dev)[:N]  # non-null even for N = 0
+        self.N, self.cam = N, cam
+        # non-null even for N = 0; ``records=False``: the caller holds the records already (bin_sort)
+        self.splats = torch.empty(max(N, 1), SPLAT_FLOATS, dtype=torch.float32, device=dev)[:N] if records else None
         self.radii = torch.empty(N, dtype=torch.int32, device=dev) if want_radii else None
         self.group_base = torch.empty(max(lib.tgs_num_groups(N), 1), dtype=torch.int32, device=dev)
         self.tile_start = torch.empty(T + 1 + 512, dtype=torch.int32, device=dev)[:T + 1]   # + 512 scratch ints of the rasterizer (tgs.h)
@@ -239,9 +224,27 @@ class FrontBuffers:
         # tile_start tensor object so that the (tile_start, sorted_gid) pair keeps its meaning for callers
         self.tile_start.tile_order = torch.empty(lib.tgs_tile_order_len(cam.W, cam.H), dtype=torch.int32, device=dev)
         self.tile_start.slot_ok = None     # quadrant bitmaps K6 leaves for K7 (rasterize_fwd allocates and fills them)
-        self.sorted_gid = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        self.scratch = torch.empty(lib.tgs_sort_scratch_bytes(cap), dtype=torch.uint8, device=dev)
+        self.size_lists(cap, dev)
         self.cleared = False     # counters + status word already cleared (by the previous frame's scan launch)
+
+    def size_lists(self, cap: int, dev) -> None:
+        """(Re-)allocate what scales with the intersection capacity: the sorted lists and the sort's scratch."""
+        self.cap = cap
+        self.sorted_gid = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        self.scratch = torch.empty(_lib.load().tgs_sort_scratch_bytes(cap), dtype=torch.uint8, device=dev)
+
+    def settle(self, budget: IntersectBudget) -> bool:
+        """After the front half was launched into these buffers: the frame's status words go to ``budget``; a synchronous
+        budget reads them back, and a frame that overflowed grows the capacity and the lists -> True = launch it again."""
+        budget.last_status, budget.last_status4 = self.status, self.status4
+        if not budget.sync:
+            return False
+        n, ovf, need, budget.last_longest = self.status4.tolist()
+        budget.last_n, budget.last_need = n, max(n, need)
+        if ovf:
+            budget.capacity = int(n * budget.growth) + 1024
+            self.size_lists(budget.capacity, self.sorted_gid.device)
+        return bool(ovf)
 
 
 def project_bin_sort(cam: Camera, means, log_scales, quats, opac_logit, sh, sh_deg: int,
@@ -275,9 +278,9 @@ def project_bin_sort(cam: Camera, means, log_scales, quats, opac_logit, sh, sh_d
     if fb is None:
         fb = FrontBuffers(cam, N, cap, want_radii, dev)
     splats, radii, group_base, tile_start = fb.splats, fb.radii, fb.group_base, fb.tile_start
-    tile_cursor, status, status4, tile_order = fb.tile_cursor, fb.status, fb.status4, fb.tile_start.tile_order
-    sorted_gid, scratch = fb.sorted_gid, fb.scratch
+    tile_cursor, status, tile_order = fb.tile_cursor, fb.status, fb.tile_start.tile_order
     while True:
+        cap, sorted_gid, scratch = fb.cap, fb.sorted_gid, fb.scratch
         if from_front:
             nf = next_front if (_SIDE_CLEAR and next_front is not None and not next_front.cleared and next_front is not fb and
                                 lib.tgs_front_can_clear_next(N, next_front.cam.W, next_front.cam.H)) else None
@@ -309,19 +312,8 @@ def project_bin_sort(cam: Camera, means, log_scales, quats, opac_logit, sh, sh_d
                                                   ptr(budget.sticky_word(dev)), budget.list_hint(), ptr(colors.colors),
                                                   ptr(colors.tag_word), colors.tag, _stream()),
                   "tgs_project_bin_sort_colors")
-        budget.last_status = status
-        budget.last_status4 = status4
-        if not budget.sync:
-            break
-        n, ovf, need, budget.last_longest = status4.tolist()
-        budget.last_n, budget.last_need = n, max(n, need)
-        if not ovf:
-            break
-        cap = int(n * budget.growth) + 1024
-        budget.capacity = cap
-        sorted_gid = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        scratch = torch.empty(lib.tgs_sort_scratch_bytes(cap), dtype=torch.uint8, device=dev)
-    return splats, radii, group_base, tile_start, sorted_gid, status
+        if not fb.settle(budget):
+            return splats, radii, group_base, tile_start, sorted_gid, status
 
 
 def _tile_start_len(tile_start) -> int:
@@ -340,14 +332,15 @@ def raster_opts(k6_blocks=None, k6_split=None, k7_front_to_back=None, k7_quad=No
                               f(k6_split_floor), f(k6_split_heads))
 
 
-def _check_tile_start(tile_start, T: int) -> None:
+def _check_tile_start(tile_start, T: int) -> int:
     """The rasterizer keeps 512 scratch ints behind the T + 1 tile starts (tgs.h, tgs_tile_start_len): a tensor that was
     copied out of the buffer ``bin_sort`` / ``FrontBuffers`` allocated (clone, contiguous, .to) has lost them.  (The C
-    ABI checks the same length; this gives the Python caller the reason.)"""
+    ABI checks the same length; this gives the Python caller the reason.)  -> that length, for the C call."""
     have = _tile_start_len(tile_start)
     if have < T + 1 + 512:
         raise ValueError(f"tile_start must be (a view of) a buffer of T + 513 = {T + 513} int32 (got room for {have}): "
                          "pass the tensor ops.bin_sort / ops.project_bin_sort returned, not a copy")
+    return have
 
 
 def rasterize_fwd(cam: Camera, splats, sorted_gid, tile_start, want_idx: bool = False, want_stop: bool = True, opts=None):
@@ -358,7 +351,7 @@ def rasterize_fwd(cam: Camera, splats, sorted_gid, tile_start, want_idx: bool = 
     lib = _lib.load()
     dev = splats.device
     H, W = cam.H, cam.W
-    _check_tile_start(tile_start, cam.num_tiles)
+    ts_len = _check_tile_start(tile_start, cam.num_tiles)
     rgb = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(H, W, dtype=torch.float32, device=dev)
     fT = torch.empty(H, W, dtype=torch.float32, device=dev)
@@ -374,7 +367,7 @@ def rasterize_fwd(cam: Camera, splats, sorted_gid, tile_start, want_idx: bool = 
         # backward over the same lists (rasterize_bwd*) skips the rest.  Results are unaffected.
         slot_ok = torch.empty(4 * lib.tgs_slot_ok_len(W, H, sorted_gid.shape[0]), dtype=torch.int64, device=dev)
         tile_start.slot_ok = slot_ok
-    check(lib.tgs_rasterize_fwd(C.byref(cs), ptr(splats), ptr(sorted_gid), ptr(tile_start), _tile_start_len(tile_start),
+    check(lib.tgs_rasterize_fwd(C.byref(cs), ptr(splats), ptr(sorted_gid), ptr(tile_start), ts_len,
                                 ptr(getattr(tile_start, "tile_order", None)), ptr(rgb),
                                 ptr(depth), ptr(fT), ptr(fidx), ptr(stop), ptr(slot_ok),
                                 C.byref(opts) if opts is not None else None, _stream()), "tgs_rasterize_fwd")
@@ -391,7 +384,7 @@ def rasterize_depth_stats(cam: Camera, splats, sorted_gid, tile_start, depth_acc
     lib = _lib.load()
     dev = splats.device
     H, W = cam.H, cam.W
-    _check_tile_start(tile_start, cam.num_tiles)
+    ts_len = _check_tile_start(tile_start, cam.num_tiles)
     depth_acc, fT = _f32c(depth_acc.detach()), _f32c(final_T.detach())
     if tuple(depth_acc.shape) != (H, W) or tuple(fT.shape) != (H, W):
         raise ValueError(f"depth_acc / final_T must be [{H},{W}]")
@@ -400,7 +393,7 @@ def rasterize_depth_stats(cam: Camera, splats, sorted_gid, tile_start, depth_acc
     med = torch.empty(H, W, dtype=torch.float32, device=dev)
     gid = torch.empty(H, W, dtype=torch.int32, device=dev) if want_gid else None
     cs = cam.c_struct()
-    check(lib.tgs_rasterize_depth_stats(C.byref(cs), ptr(splats), ptr(sorted_gid), ptr(tile_start), _tile_start_len(tile_start),
+    check(lib.tgs_rasterize_depth_stats(C.byref(cs), ptr(splats), ptr(sorted_gid), ptr(tile_start), ts_len,
                                         ptr(getattr(tile_start, "tile_order", None)), ptr(depth_acc), ptr(fT), ptr(stop),
                                         ptr(var), ptr(med), ptr(gid), C.byref(opts) if opts is not None else None,
                                         _stream()), "tgs_rasterize_depth_stats")
@@ -417,7 +410,7 @@ def rasterize_bwd(cam: Camera, splats, group_base, sorted_gid, tile_start, rgb, 
     """
     lib = _lib.load()
     dev = splats.device
-    _check_tile_start(tile_start, cam.num_tiles)
+    ts_len = _check_tile_start(tile_start, cam.num_tiles)
     if partials is None:     # (a caller may hand in the buffer, e.g. pre-filled to detect reads of unwritten records)
         partials = torch.empty(sorted_gid.shape[0], PARTIAL_FLOATS, dtype=torch.float32, device=dev)
     tile_loss = torch.empty(cam.num_tiles, 2, dtype=torch.float32, device=dev) if want_tile_loss else None
@@ -428,7 +421,7 @@ def rasterize_bwd(cam: Camera, splats, group_base, sorted_gid, tile_start, rgb, 
         ls = _loss_spec_struct(loss, keep)
     v_rgb, v_depth, v_alpha = _f32c(v_rgb), _f32c(v_depth), _f32c(v_alpha)
     check(lib.tgs_rasterize_bwd(C.byref(cs), ptr(splats), ptr(group_base), ptr(sorted_gid),
-                                ptr(tile_start), _tile_start_len(tile_start), ptr(getattr(tile_start, "tile_order", None)),
+                                ptr(tile_start), ts_len, ptr(getattr(tile_start, "tile_order", None)),
                                 ptr(rgb), ptr(depth), ptr(fT), ptr(_stop_pos_of(fT, stop_pos)),
                                 ptr(v_rgb), ptr(v_depth), ptr(v_alpha),
                                 C.byref(ls) if ls is not None else None, ptr(partials),
