@@ -565,6 +565,41 @@ int tgs_adam_step(int N, int sh_stride, float* params, const float* grads, float
                   int64_t elem_begin, int64_t elem_end,
                   const int32_t* skip_if_overflow /*status[2] of the frame, or NULL*/, void* stream);
 
+/* Fixed-budget MCMC strategy (3DGS-MCMC, Kheradmand et al. 2024; an ADDITION within TGS_VERSION 320: a new struct and two
+ *     new calls, nothing earlier changes; csrc/mcmc.hip, touch_gs_amd/mcmc.py).
+ * tgs_mcmc_adam_geom: ONE launch, a thread per Gaussian, over the GEOMETRY segments of the flat layout (means, log_scales,
+ *     quats, opac_logit); the SH segment, its moments and every pad are not written -- step them with
+ *     tgs_adam_step(elem_begin = start of sh, elem_end = -1).  Per Gaussian, with o = sigmoid(ol) and s_j = exp(ls_j) of
+ *     the parameters BEFORE the update:
+ *        g_ol   += opacity_reg / N * o (1 - o)          g_ls_j += scale_reg / (3 N) * s_j
+ *     (the gradients of opacity_reg * mean(o) + scale_reg * mean(s)); then the Adam update of tgs_adam_step on the 11 values
+ *     with g' = grad_scale (g + reg) -- the same device function, so with both weights 0 and noise NULL the results equal
+ *     tgs_adam_step(0, start of sh) bit for bit; then, if noise != NULL, from the UPDATED values o', s', q':
+ *        t = gate_k (o' - gate_o0),  gate = 0 if t > 80, else 1 / (1 + exp(t)),  R = R(q' / |q'|)
+ *        means += (noise_lr * lr_means * gate) * R diag(s'^2) R^T n,    n = noise[g] (standard normal draws of the caller)
+ *     with lr_means the one the Adam update used (spec->device_bias_corr[2] where that is given).  A frame whose guard
+ *     word has its overflow flag set makes the launch a no-op.  No atomics: the same inputs give the same bits.
+ * tgs_mcmc_relocate: gsplat's compute_relocation for n rows, in place, a thread per row.  ratio[i] <= 1: row i is not
+ *     touched.  Otherwise r = min(ratio[i], 51), o = sigmoid(ol):
+ *        x = 1 - (1 - o)^(1/r),   S = sum_{i=1..r} sum_{k=0..i-1} C(i-1, k) (-1)^k x^(k+1) / sqrt(k+1)
+ *        ol <- logit(clamp(x, min_opacity, 1 - 2^-23)),   ls_j <- ls_j + log(o / S)
+ *     evaluated in fp64 from the fp32 inputs and rounded once (naive fp32 is wrong by 2e-4 relative at both ends of the
+ *     opacity range: the sum cancels to 1 / 2.9e4 of its terms at o = 1 - 2^-23, r = 51).
+ * Both check every argument before any launch; accuracy: tests/test_gpu_mcmc.py against tests/mcmc_ref.py. */
+typedef struct TgsMcmcSpec {
+  float opacity_reg;   /* lambda_o (gsplat: 0.01) */
+  float scale_reg;     /* lambda_s (0.01) */
+  float noise_lr;      /* 5e5; the noise is scaled by noise_lr * (the resolved lr_means of the Adam spec) */
+  float gate_k;        /* 100 */
+  float gate_o0;       /* 0.005 */
+} TgsMcmcSpec;
+int tgs_mcmc_adam_geom(int N, int sh_stride, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                       const TgsAdamSpec* spec /*[host]*/, float grad_scale, const TgsMcmcSpec* mcmc /*[host]*/,
+                       const float* noise /*[N,3] standard normal, or NULL = no noise*/,
+                       const int32_t* skip_if_overflow /*status[2] of the frame, or NULL*/, void* stream);
+int tgs_mcmc_relocate(int n, const int32_t* ratio /*[n], >= 1*/, float* opac_logit /*[n], in place*/,
+                      float* log_scales /*[n,3], in place*/, float min_opacity, void* stream);
+
 /* K10 SSIM (11x11 Gaussian window, sigma 1.5, zero padding) forward + gradient image; the
  *     (1-SSIM) term of the Splatfacto-style loss.
  * out: block_partials[ceil(H/16)*ceil(W/16)] per-tile sums of the SSIM map (deterministic;

@@ -47,6 +47,12 @@ class TgsAdamSpec(C.Structure):
                 ("bias_corr1", C.c_float), ("bias_corr2", C.c_float), ("device_bias_corr", C.c_void_p)]
 
 
+class TgsMcmcSpec(C.Structure):
+    """Regulariser weights and noise constants of tgs_mcmc_adam_geom (tgs.h)."""
+    _fields_ = [("opacity_reg", C.c_float), ("scale_reg", C.c_float), ("noise_lr", C.c_float), ("gate_k", C.c_float),
+                ("gate_o0", C.c_float)]
+
+
 class TgsGpisView(C.Structure):
     """One view of tgs_gpis_render (tgs.h): camera, region of interest, march."""
     _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
@@ -120,6 +126,8 @@ SIGNATURES = {
     "tgs_adam_step_sh_gathered": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(TgsAdamSpec), C.c_float, _P, _P]),
     "tgs_store_small": (C.c_int, [_P, C.POINTER(C.c_float), _I, _P]),
     "tgs_adam_step": (C.c_int, [_I, _I, _P, _P, _P, _P, C.POINTER(TgsAdamSpec), C.c_float, C.c_int64, C.c_int64, _P, _P]),
+    "tgs_mcmc_adam_geom": (C.c_int, [_I, _I, _P, _P, _P, _P, C.POINTER(TgsAdamSpec), C.c_float, C.POINTER(TgsMcmcSpec), _P, _P, _P]),
+    "tgs_mcmc_relocate": (C.c_int, [_I, _P, _P, _P, C.c_float, _P]),
     "tgs_ssim_fwd_bwd": (C.c_int, [_I, _I, _P, _P, C.c_float, _P, _P, _P, _P]),
     "tgs_ssim_fwd_bwd_rows": (C.c_int, [_I, _I, _P, _P, C.c_float, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
     "tgs_set_ssim_form": (C.c_int, [_I]),

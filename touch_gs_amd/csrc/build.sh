@@ -6,7 +6,7 @@ OUT="$HERE/../lib"
 mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wall -Wno-unused-function $TGS_EXTRA_FLAGS"
-SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gpis tsdf peer"
+SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gpis tsdf peer mcmc"
 # raster.hip: the SLP vectoriser pairs the per-pixel FMAs into v_pk_fma_f32, which on gfx950 costs
 # 1.84x a plain v_fma_f32 and needs register-pair shuffles (v_mov) around it: K7 127 -> 100 VGPRs and
 # -7 % time, K6 -3 % without it (measured, same box)
@@ -22,8 +22,10 @@ SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gp
 # recomputes the compensated image instead of reading it and must form the bits SSIM saw, so that sign() decides alike.
 # tsdf.hip: -ffp-contract=off: every product and sum rounds on its own, as the fp32 NumPy emulation of tests/tsdf_ref.py
 # evaluates them (the emulation's measured error is then the kernel's); the kernels are HBM-bound.
+# mcmc.hip: -ffp-contract=off for the same reason (tests/mcmc_ref.py emulates the noise term); the Adam update inside it is
+# adam1's explicit fmaf chain whatever the flag, which keeps it bit-identical to K9.
 declare -A EXTRA=([raster]="-fno-slp-vectorize" [imgloss]="-fno-slp-vectorize" [project]="-ffp-contract=on"
-                  [depthnormal]="-ffp-contract=on" [exposure]="-ffp-contract=on" [tsdf]="-ffp-contract=off")
+                  [depthnormal]="-ffp-contract=on" [exposure]="-ffp-contract=on" [tsdf]="-ffp-contract=off" [mcmc]="-ffp-contract=off")
 pids=()
 for s in $SRCS; do
   [ -f "$HERE/$s.hip" ] || continue

@@ -110,6 +110,12 @@ class ModelConfig:
     exposure_lr: float = 0.0
     exposure_l2: float = 0.0
     exposure_start_step: int = 0
+    # fixed-budget MCMC strategy (touch_gs_amd.mcmc): weights of the L1 regularisers on opacity and scale and
+    # the rate of the noise on the means (times lr_means), written by ``enable_mcmc`` from its MCMCConfig.  All 0 = off: no
+    # launch, nothing changes
+    opacity_reg: float = 0.0
+    scale_reg: float = 0.0
+    mcmc_noise_lr: float = 0.0
 
     def downscale_factor(self, step: int) -> int:
         """2 ** max(num_downscales - step // resolution_schedule, 0)  (Splatfacto._get_downscale_factor)."""
@@ -127,6 +133,10 @@ class ModelConfig:
     def lrs(self) -> Dict[str, float]:
         return dict(means=self.lr_means, log_scales=self.lr_scales, quats=self.lr_quats,
                     opac_logit=self.lr_opac, sh_dc=self.lr_sh_dc, sh_rest=self.lr_sh_rest)
+
+
+def mcmc_configured(c: ModelConfig) -> bool:
+    return c.opacity_reg > 0 or c.scale_reg > 0 or c.mcmc_noise_lr > 0
 
 
 @dataclasses.dataclass(frozen=True)
@@ -231,7 +241,8 @@ class DepthGaussianSplattingModel:
         self._pose_scratch = None
         self.exposure_set = None    # enable_exposure(views)
         # every other field the train step keeps between calls is declared HERE: no method creates an attribute
-        self.density = None         # enable_densification(): the DensityController
+        self.density = None         # enable_densification(): the DensityController | enable_mcmc(): the MCMCController
+        self.mcmc = self._mcmc_gen = None   # enable_mcmc(): the TgsMcmcSpec of the step's kernel | the device generator of its noise
         self.last_refine = self._refined_at = None      # what the last density.refine reported, and the step it ran at
         self._recent_cams = collections.OrderedDict()   # id -> full-resolution camera of the last <= 16 steps (spatial_sort)
         self._last_downscale = None     # coarse-to-fine factor of the previous step; None = no step yet, no change of level
@@ -678,9 +689,46 @@ class DepthGaussianSplattingModel:
         self._refines_since_sort = 0
         return perm
 
+    def enable_mcmc(self, cfg=None):
+        """Train with the fixed-budget MCMC strategy (touch_gs_amd.mcmc) instead of clone / split / cull: ``density`` becomes
+        the MCMCController, and every single-process ``train_step`` runs the unfused backward followed by ONE launch that
+        does regularisers + geometry Adam + noise (ops.mcmc_adam_geom) and the SH Adam.  The mode gives up the fused K8+Adam
+        kernel with its colour / front prefetch (the noise moves the means after the optimizer: a prefetched K1 would be
+        stale), step graphs and data-parallel steps.  -> the controller."""
+        from .mcmc import MCMCConfig, MCMCController
+        cfg = cfg or MCMCConfig()
+        if self.density is not None and not isinstance(self.density, MCMCController):
+            raise ValueError("the MCMC strategy (enable_mcmc) does not combine with enable_densification: one refinement "
+                             "strategy per model")
+        if self._graphs:
+            raise ValueError("the MCMC strategy (enable_mcmc) does not combine with capture_step_graphs: the captured step "
+                             "is the fused one and has no noise draw")
+        dev = self.params.flat.device
+        c = self.config
+        c.opacity_reg, c.scale_reg, c.mcmc_noise_lr = cfg.opacity_reg, cfg.scale_reg, cfg.noise_lr
+        self.density = MCMCController(cfg, self.params.N, dev)
+        self.mcmc = cfg.spec()
+        self._mcmc_gen = torch.Generator(device=dev).manual_seed(cfg.seed)
+        self._prefetch_ready = None
+        return self.density
+
+    def _mcmc_step(self, guard) -> None:
+        """The optimizer half of an MCMC step from ``params.grad``: one launch for the geometry (regularisers, Adam, noise
+        from this model's generator), the SH rows through K9."""
+        opt = self.optimizer
+        opt.begin_step()
+        noise = None
+        if self.mcmc.noise_lr > 0:
+            noise = torch.randn(self.params.N, 3, generator=self._mcmc_gen, device=self.params.flat.device, dtype=torch.float32)
+        ops.mcmc_adam_geom(opt, self.mcmc, noise, guard=guard)
+        opt.step_range(opt.geom_end(), -1, guard=guard)
+
     def enable_densification(self, cfg=None):
         """Turn on Splatfacto-style clone / split / cull refinement (touch_gs_amd.densify)."""
         from .densify import DensifyConfig, DensityController
+        if self.mcmc is not None:
+            raise ValueError("enable_densification does not combine with the MCMC strategy (enable_mcmc): one refinement "
+                             "strategy per model")
         self.density = DensityController(cfg or DensifyConfig(), self.params.N, self.params.flat.device)
 
     # -- sync-free intersection budget ---------------------------------------------------------
@@ -795,6 +843,9 @@ class DepthGaussianSplattingModel:
         if self.exposure_set is not None or self.config.exposure_lr > 0:
             raise ValueError("capture_step_graphs does not combine with exposure compensation (exposure_lr): the captured "
                              "step has no exposure launches")
+        if self.mcmc is not None or mcmc_configured(self.config):
+            raise ValueError("capture_step_graphs does not combine with the MCMC strategy (enable_mcmc / opacity_reg, scale_reg, "
+                             "mcmc_noise_lr): the captured step is the fused one and has no noise draw")
         if not opt.can_fuse_with_backward(deg):
             raise RuntimeError("step graphs need the fused K8+K9 path (dense SH at its full degree 1 or 3)")
         p = self.params
@@ -838,7 +889,15 @@ class DepthGaussianSplattingModel:
         pre, self._prefetch_ready = self._prefetch_ready, None
         if self._graphs and not distributed and density is None and self._replay_graph(view, deg):
             return
-        fuse = (not distributed) and self.fuse_adam and opt.can_fuse_with_backward(deg)
+        mcmc = self.mcmc
+        if mcmc is None and mcmc_configured(self.config):
+            raise ValueError("opacity_reg / scale_reg / mcmc_noise_lr are set but the MCMC strategy is not enabled: call "
+                             "model.enable_mcmc(cfg) before the first train_step")
+        if mcmc is not None and distributed:
+            raise ValueError("the MCMC strategy (enable_mcmc) is not supported in data-parallel steps (dp.active)")
+        # MCMC mode: the unfused backward leaves the gradient in params.grad for the regulariser + Adam + noise launch; no
+        # prefetch is armed (the noise moves the means after the optimizer)
+        fuse = (not distributed) and mcmc is None and self.fuse_adam and opt.can_fuse_with_backward(deg)
         factored = distributed and self.dp_factored_sh and opt.can_gather_sh()
         if self.budget.speculative and distributed and not factored:
             raise RuntimeError("the speculative intersection budget does not combine with the dense (flat all-reduce) "
@@ -850,7 +909,7 @@ class DepthGaussianSplattingModel:
         colors = pre if (pre is not None and (fuse or (factored and pre.front_issued and not pre.colors_valid))
                          and pre.matches(self.tuned(view.cam), self.params.N, deg)) else None
         arm = self._arm_prefetch(next_view, deg, fuse, factored, in_use=colors if fuse else pre)
-        self.forward_backward(view, want_v_xy=density is not None, fuse_adam=fuse, color_block=block,
+        self.forward_backward(view, want_v_xy=density is not None and mcmc is None, fuse_adam=fuse, color_block=block,
                               colors=colors, prefetch=arm if fuse else None,
                               next_front=arm.front if arm is not None else None, pose_grad=pose_on, exposure=expo_row)
         self._prefetch_ready = arm
@@ -865,6 +924,8 @@ class DepthGaussianSplattingModel:
             self._factored_tail(dp, view, deg, arm)
         elif distributed:
             dp.reduce_and_step(self.params.grad, opt.step_range, opt.begin_step)
+        elif mcmc is not None:
+            self._mcmc_step(self.last["guard"])
         elif not fuse:
             opt.step(guard=self.last["guard"])
         self.step += 1
@@ -1051,6 +1112,8 @@ class DepthGaussianSplattingModel:
             sd["pose"] = self.pose_refiner.state_dict(self)
         if self.exposure_set is not None:   # likewise
             sd["exposure"] = self.exposure_set.state_dict()
+        if self.mcmc is not None:           # likewise: the noise stream goes on where it stopped
+            sd["mcmc"] = dict(generator=self._mcmc_gen.get_state())
         return sd
 
     def load_state_dict(self, sd):
@@ -1078,6 +1141,8 @@ class DepthGaussianSplattingModel:
         # and render every view uncompensated (held-out views have no row); a set of another size is refused by the set
         if self.exposure_set is not None and sd.get("exposure") is not None:
             self.exposure_set.load_state_dict(sd["exposure"])
+        if self.mcmc is not None and sd.get("mcmc") is not None:
+            self._mcmc_gen.set_state(sd["mcmc"]["generator"].cpu())
 
 
 class _SSIM(torch.autograd.Function):

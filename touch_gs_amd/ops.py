@@ -1246,3 +1246,81 @@ def apply_exposure(rgb, E):
     if E.shape != (3, 4):
         raise ValueError(f"apply_exposure: E must be [3,4], got {tuple(E.shape)}")
     return _ApplyExposure.apply(rgb, E)
+
+
+# ------------------------------------------------------------------------------------------------
+# fixed-budget MCMC strategy (csrc/mcmc.hip, touch_gs_amd/mcmc.py)
+# ------------------------------------------------------------------------------------------------
+def mcmc_spec(opacity_reg: float = 0.01, scale_reg: float = 0.01, noise_lr: float = 5e5, gate_k: float = 100.0,
+              gate_o0: float = 0.005) -> "_lib.TgsMcmcSpec":
+    """The TgsMcmcSpec of :func:`mcmc_adam_geom` (defaults: gsplat's MCMC trainer)."""
+    s = _lib.TgsMcmcSpec()
+    s.opacity_reg, s.scale_reg, s.noise_lr, s.gate_k, s.gate_o0 = opacity_reg, scale_reg, noise_lr, gate_k, gate_o0
+    return s
+
+
+def mcmc_adam_geom(optimizer, mcmc, noise=None, grad_scale: float = 1.0, guard=None) -> None:
+    """Regularisers + Adam on the geometry segments + noise on the means, one launch (tgs_mcmc_adam_geom): the step of
+    ``optimizer`` (a FusedAdam after ``begin_step``) from ``optimizer.p.grad``; the SH segment is the caller's
+    (``optimizer.step_range(optimizer.geom_end(), -1)``).  ``mcmc``: a TgsMcmcSpec (:func:`mcmc_spec`); ``noise``: [N,3]
+    standard normal draws on the device, or None = no noise; ``guard``: the frame's status word.  No host sync."""
+    lib = _lib.load()
+    p = optimizer.p
+    if noise is not None:
+        if noise.dtype != torch.float32 or not noise.is_contiguous() or noise.shape != (p.N, 3) or noise.device != p.flat.device:
+            raise ValueError(f"mcmc_adam_geom: noise must be a contiguous float32 [{p.N}, 3] tensor on {p.flat.device}")
+    if guard is not None and (guard.dtype != torch.int32 or guard.numel() < 2 or guard.device != p.flat.device):
+        raise ValueError("mcmc_adam_geom: guard must be the frame's int32 status word on the parameters' device")
+    s = optimizer._spec()
+    check(lib.tgs_mcmc_adam_geom(p.N, p.K, ptr(p.flat), ptr(p.grad), ptr(optimizer.exp_avg), ptr(optimizer.exp_avg_sq),
+                                 C.byref(s), C.c_float(grad_scale), C.byref(mcmc), ptr(noise), ptr(guard), _stream()),
+          "tgs_mcmc_adam_geom")
+
+
+_RELOC_MAX = 51
+_RELOC_TABLE = None
+
+
+def _reloc_table():
+    """[52, 51] float64: row r, column k = C(r, k+1) (-1)^k / sqrt(k+1) for k < r, else 0."""
+    global _RELOC_TABLE
+    if _RELOC_TABLE is None:
+        t = torch.zeros(_RELOC_MAX + 1, _RELOC_MAX, dtype=torch.float64)
+        for r in range(1, _RELOC_MAX + 1):
+            for k in range(r):
+                t[r, k] = float(math.comb(r, k + 1)) * (-1.0) ** k / math.sqrt(k + 1)
+        _RELOC_TABLE = t
+    return _RELOC_TABLE
+
+
+def mcmc_relocate(ratio, opac_logit, log_scales, min_opacity: float = 0.005) -> None:
+    """gsplat's ``compute_relocation`` in place on rows that are split ``ratio`` ways (int32 [n], >= 1; 1 = untouched):
+    new opacity x = 1 - (1 - o)^(1/r), r = min(ratio, 51), clamped to [min_opacity, 1 - 2^-23], and scales times o / S
+    with S = sum_{k<r} C(r, k+1) (-1)^k x^(k+1) / sqrt(k+1), in fp64, rounded once (tgs_mcmc_relocate).  ``opac_logit`` [n],
+    ``log_scales`` [n,3]: contiguous float32, written in place.  CPU tensors: the same single sum in torch fp64 (host-side
+    callers and tests; the training path is on the device)."""
+    n = opac_logit.shape[0]
+    if not (0.0 < min_opacity < 1.0):
+        raise ValueError("mcmc_relocate: min_opacity must lie in (0, 1)")
+    if (ratio.dtype != torch.int32 or ratio.shape != (n,) or opac_logit.dtype != torch.float32 or log_scales.dtype != torch.float32
+            or log_scales.shape != (n, 3) or not (ratio.is_contiguous() and opac_logit.is_contiguous() and log_scales.is_contiguous())
+            or not (ratio.device == opac_logit.device == log_scales.device)):
+        raise ValueError("mcmc_relocate: need ratio int32 [n], opac_logit float32 [n], log_scales float32 [n,3], contiguous, on one device")
+    if opac_logit.is_cuda:
+        check(_lib.load().tgs_mcmc_relocate(n, ptr(ratio), ptr(opac_logit), ptr(log_scales), C.c_float(min_opacity), _stream()),
+              "tgs_mcmc_relocate")
+        return
+    sel = torch.nonzero(ratio > 1).squeeze(1)
+    if sel.numel() == 0:
+        return
+    r = ratio[sel].clamp(max=_RELOC_MAX).long()
+    l = opac_logit[sel].double()
+    log_1mo = -torch.nn.functional.softplus(l, beta=1.0, threshold=1e9)        # log(1 - sigmoid(l))
+    o = torch.sigmoid(l)
+    x = -torch.expm1(log_1mo / r.double())
+    pw = x[:, None] ** torch.arange(1, _RELOC_MAX + 1, dtype=torch.float64)[None, :]
+    S = (_reloc_table()[r] * pw).sum(1)
+    lo = float(torch.tensor(min_opacity, dtype=torch.float32))      # the C float argument carries the fp32 rounding
+    xc = x.clamp(min=lo, max=1.0 - 2.0 ** -23)
+    opac_logit[sel] = (torch.log(xc) - torch.log1p(-xc)).float()
+    log_scales[sel] = (log_scales[sel].double() + torch.log(o / S)[:, None]).float()

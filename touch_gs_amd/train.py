@@ -236,6 +236,15 @@ def main(argv=None, view_hook=None):
                          "colour transform (INRIA's exposure_lr is 0.01); 0 = off (the default under both presets)")
     ap.add_argument("--exposure-l2", type=float, default=0.0, help="pull of the exposure matrices towards the identity")
     ap.add_argument("--exposure-start-step", type=int, default=0, help="first step that compensates and learns exposures")
+    ap.add_argument("--strategy", type=str, default="default", choices=("default", "mcmc"),
+                    help="refinement strategy: default = Splatfacto's clone / split / cull (--densify); mcmc = fixed-budget "
+                         "3DGS-MCMC (touch_gs_amd/mcmc.py): relocation of dead Gaussians, growth by 5 %% up to --cap-max, opacity "
+                         "and scale regularisers and noise on the means every step; single process only")
+    ap.add_argument("--cap-max", type=int, default=1_000_000, help="mcmc: the largest number of Gaussians")
+    ap.add_argument("--mcmc-noise-lr", type=float, default=5e5, help="mcmc: rate of the noise on the means (times the position rate)")
+    ap.add_argument("--opacity-reg", type=float, default=0.01, help="mcmc: weight of the mean opacity in the loss")
+    ap.add_argument("--scale-reg", type=float, default=0.01, help="mcmc: weight of the mean scale in the loss")
+    ap.add_argument("--mcmc-min-opacity", type=float, default=0.005, help="mcmc: a Gaussian at or below this opacity is dead")
     args = ap.parse_args(argv)
 
     few = args.preset == "few-view"
@@ -243,6 +252,7 @@ def main(argv=None, view_hook=None):
         args.uncertainty_floor = 0.05 if few else 0.0
     if args.cull_unseen is None:
         args.cull_unseen = few
+    use_mcmc = args.strategy == "mcmc"
     dp = parallel.init_from_env()
     dev = torch.device("cuda", dp.local_rank)
     torch.cuda.set_device(dev)
@@ -277,7 +287,9 @@ def main(argv=None, view_hook=None):
                       mono_depth_patch_min_var=args.mono_depth_patch_min_var, normal_prior_mult=args.normal_mult,
                       normal_max_jump=args.normal_max_jump, pose_lr_rot=args.pose_lr_rot, pose_lr_trans=args.pose_lr_trans,
                       pose_l2_rot=args.pose_l2_rot, pose_l2_trans=args.pose_l2_trans, pose_start_step=args.pose_start_step,
-                      exposure_lr=args.exposure_lr, exposure_l2=args.exposure_l2, exposure_start_step=args.exposure_start_step)
+                      exposure_lr=args.exposure_lr, exposure_l2=args.exposure_l2, exposure_start_step=args.exposure_start_step,
+                      opacity_reg=args.opacity_reg if use_mcmc else 0.0, scale_reg=args.scale_reg if use_mcmc else 0.0,
+                      mcmc_noise_lr=args.mcmc_noise_lr if use_mcmc else 0.0)
     model = DepthGaussianSplattingModel(cfg, params)
     train_views = [views[i] for i in i_train]
     train_names = [f"view_{i}" for i in i_train] if args.synthetic else [scene.names[i] for i in i_train]
@@ -285,19 +297,26 @@ def main(argv=None, view_hook=None):
         raise ValueError("--pose-lr-rot / --pose-lr-trans: pose refinement is not supported in data-parallel runs")
     if cfg.exposure_lr > 0 and dp.active:
         raise ValueError("--exposure-lr: exposure compensation is not supported in data-parallel runs")
+    if use_mcmc and dp.active:
+        raise ValueError("--strategy mcmc: the MCMC strategy is not supported in data-parallel runs")
     if view_hook is not None:
         view_hook(train_views, 1.0 if args.synthetic else scene.scale)
     model.enable_pose_refinement(train_views)     # held-out views are never refined; before a checkpoint is loaded
     model.enable_exposure(train_views)            # likewise: held-out views have no row and are rendered uncompensated
     if cfg.spatial_sort:
         model.spatial_sort()
-    if args.densify:
+    if use_mcmc:
+        from .mcmc import MCMCConfig
+        model.enable_mcmc(MCMCConfig(cap_max=args.cap_max, refine_every=args.refine_every, warmup_length=args.warmup_length,
+                                     min_opacity=args.mcmc_min_opacity, opacity_reg=args.opacity_reg, scale_reg=args.scale_reg,
+                                     noise_lr=args.mcmc_noise_lr, seed=args.seed, num_train_data=len(i_train)))
+    elif args.densify:
         from .densify import DensifyConfig
         model.enable_densification(DensifyConfig(refine_every=args.refine_every, warmup_length=args.warmup_length,
                                                  num_train_data=len(i_train), densify_grad_thresh=args.densify_grad_thresh,
                                                  cull_unseen=bool(args.cull_unseen)))
     trainer_state = dict(uncertainty_scaling=args.uncertainty_scaling, uncertainty_floor=args.uncertainty_floor, densify=bool(args.densify),
-                         num_downscales=args.num_downscales, cull_unseen=bool(args.cull_unseen))
+                         num_downscales=args.num_downscales, cull_unseen=bool(args.cull_unseen), strategy=args.strategy)
     if dp.rank == 0 and (args.uncertainty_floor > 0 or args.cull_unseen):
         print(f"note: this run deviates from the reference's objective / Splatfacto's refinement: uncertainty floor "
               f"{args.uncertainty_floor} (no depth weight above 1 / (uncertainty_weight * floor)), cull_unseen={bool(args.cull_unseen)} "
