@@ -504,6 +504,49 @@ int tgs_project_bin_sort_front(const TgsCamera* cam /*[host]*/, int N, const flo
  * -- pass counters_cleared = 1 to the optimizer call that fills them.  tgs_front_can_clear_next is always true now: */
 int tgs_front_can_clear_next(int N, int W, int H);
 
+/* Direct bins (an ADDITION within TGS_VERSION 320: three new calls, nothing earlier changes).  The K1 that runs inside
+ *     the fused optimizer kernel knows, when it counts a (Gaussian, tile) pair, everything about it except where the tile's list
+ *     starts -- which is all the fill pass of tgs_project_bin_sort_front adds, in a pass of its own over the records.  Given
+ *         bins[(xcc * T + tile) * cap + rank] = {gid, depth bits}        (8 bytes each; T = tgs_num_tiles, xcc in [0, 8))
+ *     it stores the pair at its arrival rank in the bin of its (XCC, tile) instead of remembering the rank, and
+ *     tgs_project_bin_sort_front_bins only scans and sorts: the sorts gather a tile's list from its 8 sub-bins.  Every output
+ *     (tile_start, sorted_gid, tile_order, status) is what the pair of calls without bins gives.
+ *     cap in [1, 4096] is the caller's bound on the longest tile LIST, as max_list_hint: a sub-list beyond it drops its pairs and
+ *     a list beyond it is not sorted, and either voids the frame (status[1] = 1, sticky raised) -- max_list_hint only chooses
+ *     the sort classes below cap.  Which of the two happened depends on where the groups ran: when a sub-list overflowed, the
+ *     scan empties every list before it measures them and status[3] (the longest list) reads 0, not the length that broke the
+ *     bound -- a caller that sizes its next bound from status[3] must take it from a frame binned without bins (the trainer's
+ *     replay does: it withdraws the bound, hence the bins, until it has learned a new one).  bins_len (entries of 8 bytes) must be >= tgs_bins_len(T, cap) = 8 * T * cap, checked before
+ *     any launch.  The bins need no clearing.  Both calls of a frame take the same bins and cap; scratch is still required (a
+ *     replay through tgs_project_bin_sort uses it). */
+int64_t tgs_bins_len(int T, int cap);
+/* tgs_bin_sort on records that exist, through the direct bins: the counting pass stores the pairs in the bins as the fused K1 does
+ *     (the same device code), then scan and sort.  For tests and A/B runs of the front half alone. */
+int tgs_bin_sort_bins(const TgsCamera* cam /*[host]*/, int N, float* splats, int32_t* group_base, int32_t* tile_start,
+                      int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid, int32_t* tile_order,
+                      int64_t capacity, void* scratch, int32_t* status, int32_t* sticky_overflow, int32_t max_list_hint,
+                      void* bins, int64_t bins_len, int32_t cap, void* stream);
+int tgs_project_bwd_adam_next_front_bins(const TgsCamera* cam /*[host]*/, int N, int sh_stride, int sh_deg,
+                                         float* params, float* exp_avg, float* exp_avg_sq,
+                                         const TgsAdamSpec* spec /*[host]*/, const float* splats,
+                                         const int32_t* group_base, const float* partials, float* v_xy,
+                                         const int32_t* skip_if_overflow, const TgsCamera* next_cam /*[host]*/,
+                                         float* colors_next, int32_t* tag_word, int32_t tag_value, float* splats_next,
+                                         int32_t* radii_next, int32_t* group_base_next, int32_t* tile_cursor_next,
+                                         int64_t capacity_next, void* scratch_next, int32_t* status_next,
+                                         int32_t* sticky_overflow, int counters_cleared,
+                                         void* bins, int64_t bins_len, int32_t cap, void* stream);
+int tgs_project_bin_sort_front_bins(const TgsCamera* cam /*[host]*/, int N, const float* means,
+                                    const float* log_scales, const float* quats, const float* opac_logit,
+                                    const float* sh, int sh_stride, int sh_deg, float* splats, int32_t* radii,
+                                    int32_t* group_base, int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor,
+                                    int32_t* sorted_gid, int32_t* tile_order, int64_t capacity, void* scratch,
+                                    int32_t* status, int32_t* sticky_overflow, int32_t max_list_hint,
+                                    const int32_t* tag_word, int32_t tag_expect,
+                                    const TgsCamera* next_cam /*[host] or NULL*/, int32_t* next_tile_cursor /*or NULL*/,
+                                    int32_t* next_status /*or NULL*/, const void* bins, int64_t bins_len, int32_t cap,
+                                    void* stream);
+
 /* Data-parallel step (one view per rank, SURVEY section 8 row e).  The SH gradient of a rank is the
  *     outer product Y_k(dir(g)) x v_color[g,:], so the ranks exchange v_color (all-gather, 3 floats
  *     per Gaussian and rank) instead of all-reducing 3*sh_stride floats per Gaussian:

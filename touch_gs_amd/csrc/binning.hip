@@ -37,16 +37,19 @@ __device__ __forceinline__ int group_load_scan(const CamK& cam, int N, int group
 
 // K3a: count intersections per tile; allocate the group's pair range; remember every pair's
 // arrival rank inside its tile.
+// BINS: every pair goes straight into the direct bins (tgs_binning.h) -- the counting of the fused optimizer kernel's K1, from records
+template <bool BINS>
 __global__ __launch_bounds__(TGS_GROUP) void k_tile_count(
     CamK cam, int N, float* __restrict__ splats, int32_t* __restrict__ group_base,
     int32_t* __restrict__ tile_count, int32_t* __restrict__ rank, int32_t* __restrict__ status,
-    long long capacity, int32_t* __restrict__ sticky) {
+    long long capacity, int32_t* __restrict__ sticky, uint2* __restrict__ bins, int bin_cap) {
   __shared__ GroupScan S;
   int my_off;
   const int total = group_load_scan(cam, N, tgs_group_id(), splats, S, my_off);
   const int g = tgs_group_id() * TGS_GROUP + threadIdx.x;
   if (g < N) splats[(size_t)g * TGS_SPLAT_FLOATS + 11] = __int_as_float(my_off);
-  group_count_tiles(S, cam.TW, cam.TW * cam.TH, total, group_base, tile_count, rank, status, capacity, sticky, cam.long_run);
+  group_count_tiles<BINS>(S, cam.TW, cam.TW * cam.TH, total, group_base, tile_count, rank, status, capacity, sticky, cam.long_run,
+                          bins, bin_cap);
 }
 
 // K4: exclusive scan of the [8][T] per-XCD tile counters in tile-major order -> tile_start[T+1] and
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(int T, int NB, int32_t* __r
       }
       status[0] = (int32_t)min((status[1] != 0 || voided) ? need : n, 0x7fffffffll);
       status[2] = (int32_t)min(need, 0x7fffffffll);
-      status[3] = 0;                // longest list of the frame: k_fill_bins fills it in (no Gaussians: no lists)
+      status[3] = 0;                // longest list of the frame: k_sort_tiles_wave fills it in (no Gaussians: no lists)
     }
     return;
   }
@@ -208,9 +211,7 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(int T, int NB, int32_t* __r
 __global__ __launch_bounds__(TGS_GROUP) void k_fill_bins(
     CamK cam, int N, const float* __restrict__ splats, const int32_t* __restrict__ group_base,
     const int32_t* __restrict__ sub_start, const int32_t* __restrict__ rank,
-    uint2* __restrict__ pairs, int32_t* __restrict__ status, const int32_t* __restrict__ max_list) {
-  // status[3] = the frame's longest list (complete: the scan launch has ended): what a caller sizes `max_list_hint` from
-  if (blockIdx.x == 0 && threadIdx.x == 0) status[3] = *max_list;
+    uint2* __restrict__ pairs, const int32_t* __restrict__ status) {
   if (status[1]) return;
   const int T = cam.TW * cam.TH;
   __shared__ GroupScan S;
@@ -381,15 +382,46 @@ __device__ __forceinline__ void sort_regs(u64 (&k)[E], int tid, u64* __restrict_
   }
 }
 
-template <int E, int W>
-__device__ __forceinline__ void sort_tile_regs(const u64* __restrict__ pairs, int32_t* __restrict__ sorted_gid,
+// Where the unsorted list of ONE tile lives: entry i of the list, i in [0, n).
+//   PairSrc<false>  pairs[s + i], scattered there by k_fill_bins;
+//   PairSrc<true>   the tile's 8 sub-bins, filled by K1 itself (tgs_binning.h, direct bins): the list is the concatenation of
+//                   its sub-lists, sub-list x at positions [e[x], e[x + 1]) -- e[x] = sub_start[x][tile] - s, from the scan -- and
+//                   in memory at bins[(x * T + tile) * cap ...).  The e[] are wave-uniform: loaded once per tile, they sit in
+//                   SGPRs, and a position costs 7 compare / select pairs.  An offset is clamped to the bin: a sub-list K1 cut
+//                   off at `cap` has voided the frame, and a reader of a stale list must still stay inside the buffer.
+template <bool BINS> struct PairSrc;
+template <> struct PairSrc<false> {
+  const u64* __restrict__ p;
+  __device__ __forceinline__ PairSrc(const u64* pairs, const int32_t*, int, int, int s, int) : p(pairs + s) {}
+  __device__ __forceinline__ u64 at(int i) const { return p[i]; }
+};
+template <> struct PairSrc<true> {
+  const u64* __restrict__ p;   // sub-bin of XCC 0
+  size_t xstride;              // entries between the sub-bins of consecutive XCCs
+  int cap, e[TGS_XCC];
+  __device__ __forceinline__ PairSrc(const u64* bins, const int32_t* __restrict__ sub_start, int T, int tile, int s, int cap_)
+      : p(bins + (size_t)tile * cap_), xstride((size_t)T * cap_), cap(cap_) {
+#pragma unroll
+    for (int x = 0; x < TGS_XCC; x++) e[x] = sub_start[x * T + tile] - s;
+  }
+  __device__ __forceinline__ u64 at(int i) const {
+    int x = 0, b = 0;
+#pragma unroll
+    for (int k = 1; k < TGS_XCC; k++)   // the LAST sub-list that starts at or before i (empty ones share their start with the next)
+      if (i >= e[k]) { x = k; b = e[k]; }
+    return p[x * xstride + min(i - b, cap - 1)];
+  }
+};
+
+template <int E, int W, bool BINS>
+__device__ __forceinline__ void sort_tile_regs(const PairSrc<BINS>& src, int32_t* __restrict__ sorted_gid,
                                                int s, int n, int tid, u64* __restrict__ lds) {
   constexpr int NT = TGS_WAVE * W;
   u64 k[E];
 #pragma unroll
   for (int r = 0; r < E; r++) {        // coalesced load; the initial order is irrelevant
     const int i = r * NT + tid;
-    k[r] = i < n ? pairs[s + i] : ~0ull;
+    k[r] = i < n ? src.at(i) : ~0ull;
   }
   sort_regs<E, W>(k, tid, lds);
   // sorted order: e = tid * E + r
@@ -440,10 +472,15 @@ __device__ __forceinline__ void xcd_order_regs(int T, int x, int c, int chunk,
 // max_list_hint).  A longer list means the caller's hint was wrong: the wave copies the ids UNSORTED -- valid indices,
 // so the compositing kernels run on without faulting -- and raises the overflow flag and the sticky word: the frame
 // is void exactly like one that overflowed its capacity, status[3] tells the caller what the hint should have been.
+// BINS: `pairs` are the direct bins (bin_cap entries per (XCC, tile)), read through sub_start (PairSrc<true>).
+template <bool BINS>
 __global__ __launch_bounds__(TGS_WAVE) void k_sort_tiles_wave(
     int T, const int32_t* __restrict__ tile_start, const u64* __restrict__ pairs,
     int32_t* __restrict__ sorted_gid, int32_t* __restrict__ tile_order, int n_order, int chunk,
-    int sorted_up_to, int32_t* __restrict__ status, int32_t* __restrict__ sticky, int wave_up_to) {
+    int sorted_up_to, int32_t* __restrict__ status, int32_t* __restrict__ sticky, int wave_up_to,
+    const int32_t* __restrict__ max_list, const int32_t* __restrict__ sub_start, int bin_cap) {
+  // status[3] = the frame's longest list (complete: the scan launch has ended): what a caller sizes `max_list_hint` from
+  if (blockIdx.x == 0 && threadIdx.x == 0) status[3] = *max_list;
   // the first n_order (0 or 8 x chunks per XCD) blocks build the K6 / K7 schedule of one chunk of one
   // XCD's slots each; they are the longest blocks of the launch, so they are dispatched first
   if ((int)blockIdx.x < n_order) {
@@ -454,8 +491,10 @@ __global__ __launch_bounds__(TGS_WAVE) void k_sort_tiles_wave(
   const int s = tile_start[tile];
   const int n = tile_start[tile + 1] - s;
   const int lane = threadIdx.x;
+  if (n <= 0) return;
+  const PairSrc<BINS> src(pairs, sub_start, T, tile, s, bin_cap);
   if (n > sorted_up_to) {
-    for (int i = lane; i < n; i += TGS_WAVE) sorted_gid[s + i] = (int)(pairs[s + i] & 0xffffffffull);
+    for (int i = lane; i < n; i += TGS_WAVE) sorted_gid[s + i] = (int)(src.at(i) & 0xffffffffull);
     if (lane == 0) {
       status[1] = 1;
       if (sticky) *sticky = 1;
@@ -465,19 +504,19 @@ __global__ __launch_bounds__(TGS_WAVE) void k_sort_tiles_wave(
   // lists beyond wave_up_to (512 when the four-wave launch follows, else 1024) are that launch's: a 1024-key list costs one
   // wave 864 stage x key units against 360 for 512 keys, and in an object-centric frame this launch lasts as long as its
   // longest list (round 6: k_sort_tiles_wave 24.5 -> 13 us on the 720p checkpoints)
-  if (n <= 0 || n > wave_up_to) return;
+  if (n > wave_up_to) return;
   if (n == 1) {
-    if (lane == 0) sorted_gid[s] = (int)(pairs[s] & 0xffffffffull);
+    if (lane == 0) sorted_gid[s] = (int)(src.at(0) & 0xffffffffull);
     return;
   }
   // keys per lane by list length: the network's work is (stages x keys per lane) = 21 / 56 / 144 / 360 / 864 for
   // 1 / 2 / 4 / 8 / 16 keys, so a list of 200 entries costs 0.4 of what it cost padded to 512 (round 5; the short lists are
   // the periphery of every frame and most of an object-centric one)
-  if (n <= 64) sort_tile_regs<1, 1>(pairs, sorted_gid, s, n, lane, nullptr);
-  else if (n <= 128) sort_tile_regs<2, 1>(pairs, sorted_gid, s, n, lane, nullptr);
-  else if (n <= 256) sort_tile_regs<4, 1>(pairs, sorted_gid, s, n, lane, nullptr);
-  else if (n <= 512) sort_tile_regs<8, 1>(pairs, sorted_gid, s, n, lane, nullptr);
-  else sort_tile_regs<16, 1>(pairs, sorted_gid, s, n, lane, nullptr);
+  if (n <= 64) sort_tile_regs<1, 1>(src, sorted_gid, s, n, lane, nullptr);
+  else if (n <= 128) sort_tile_regs<2, 1>(src, sorted_gid, s, n, lane, nullptr);
+  else if (n <= 256) sort_tile_regs<4, 1>(src, sorted_gid, s, n, lane, nullptr);
+  else if (n <= 512) sort_tile_regs<8, 1>(src, sorted_gid, s, n, lane, nullptr);
+  else sort_tile_regs<16, 1>(src, sorted_gid, s, n, lane, nullptr);
 }
 
 // Rare list classes (`max_list`, written by k_scan_tiles, lets both launches return at once when the
@@ -488,21 +527,24 @@ __global__ __launch_bounds__(TGS_WAVE) void k_sort_tiles_wave(
 //                      bitonic network in global memory on a power-of-two padded copy at
 //                      fb[2*s ...) (next_pow2(n) < 2n, so per-tile regions never overlap).
 // (One merged 1024-thread launch was 26 us slower on the clustered scene: one workgroup per CU.)
+template <bool BINS>
 __global__ __launch_bounds__(TGS_WAVE * 4) void k_sort_tiles_wg4(
     int T, const int32_t* __restrict__ tile_start, const u64* __restrict__ pairs,
-    int32_t* __restrict__ sorted_gid, const int32_t* __restrict__ max_list, int lo) {
+    int32_t* __restrict__ sorted_gid, const int32_t* __restrict__ max_list, int lo, int hi,
+    const int32_t* __restrict__ sub_start, int bin_cap) {
   __shared__ u64 wg_keys[TGS_WAVE * 4 * 16];   // 16 keys x 256 threads
   if (*max_list <= lo) return;
   for (int tile = blockIdx.x; tile < T; tile += gridDim.x) {
     const int s = tile_start[tile];
     const int n = tile_start[tile + 1] - s;
-    if (n <= lo || n > 4096) continue;
+    if (n <= lo || n > hi) continue;   // (hi = 4096, or the bins' capacity: the wave launch has voided a frame with a longer list)
+    const PairSrc<BINS> src(pairs, sub_start, T, tile, s, bin_cap);
     __syncthreads();
-    if (n <= 1024) { sort_tile_regs<4, 4>(pairs, sorted_gid, s, n, threadIdx.x, wg_keys); continue; }
+    if (n <= 1024) { sort_tile_regs<4, 4>(src, sorted_gid, s, n, threadIdx.x, wg_keys); continue; }
     // (1024, 2048]: 8 keys per lane -- half the network per thread; in an object-centric frame this launch lasts as long
     // as one tile's sort (a few hundred long lists, every workgroup resident at once)
-    if (n <= 2048) sort_tile_regs<8, 4>(pairs, sorted_gid, s, n, threadIdx.x, wg_keys);
-    else sort_tile_regs<16, 4>(pairs, sorted_gid, s, n, threadIdx.x, wg_keys);
+    if (n <= 2048) sort_tile_regs<8, 4>(src, sorted_gid, s, n, threadIdx.x, wg_keys);
+    else sort_tile_regs<16, 4>(src, sorted_gid, s, n, threadIdx.x, wg_keys);
   }
 }
 
@@ -518,7 +560,7 @@ __global__ __launch_bounds__(1024) void k_sort_tiles_huge(
     if (n <= 4096) continue;
     if (n <= 16384) {
       __syncthreads();
-      sort_tile_regs<16, 16>(pairs, sorted_gid, s, n, tid, wg_keys);
+      sort_tile_regs<16, 16>(PairSrc<false>(pairs, nullptr, T, tile, s, 0), sorted_gid, s, n, tid, wg_keys);
       continue;
     }
     const int np2 = next_pow2(n);
@@ -575,8 +617,12 @@ extern "C" size_t tgs_sort_scratch_bytes(int64_t capacity) {
 int tgs_bin_finish(const CamK& k, int N, const float* splats, const int32_t* group_base,
                    int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
                    int32_t* tile_order, int64_t capacity, void* scratch, int32_t* status,
-                   int32_t* sticky_overflow, int32_t max_list_hint, const BinFront* front, hipStream_t s) {
+                   int32_t* sticky_overflow, int32_t max_list_hint, const BinFront* front, hipStream_t s,
+                   const uint2* bins, int bin_cap) {
   const int T = k.TW * k.TH;
+  // direct bins: a list beyond bin_cap voids the frame, so no class beyond it is launched whatever the hint says (the
+  // `huge` class reads `pairs`, which nobody fills then: the entry points bound bin_cap by 4096)
+  if (bins && (max_list_hint < 0 || max_list_hint > bin_cap)) max_list_hint = bin_cap;
   TGS_CHECK_ARG(tile_start_len >= (int64_t)T + 1 + TGS_TILE_START_SCRATCH,
                 "tile_start buffer shorter than tgs_tile_start_len(W, H) (the scan zeroes the rasterizer's scratch behind the starts)");
   const int G = tgs_num_groups(N);
@@ -604,22 +650,37 @@ int tgs_bin_finish(const CamK& k, int N, const float* splats, const int32_t* gro
   TGS_CHECK_LAUNCH();
   if (G > 0) {
     const int32_t* max_list = tile_cursor + 2 * TGS_XCC * T + TGS_SCAN_WGS;
-    hipLaunchKernelGGL(k_fill_bins, dim3(G), dim3(TGS_GROUP), 0, s, k, N, splats, group_base,
-                       tile_cursor + TGS_XCC * T, sc.rank, (uint2*)sc.pairs, status, max_list);
-    TGS_CHECK_LAUNCH();
+    const int32_t* sub_start = tile_cursor + TGS_XCC * T;
+    if (!bins) {
+      hipLaunchKernelGGL(k_fill_bins, dim3(G), dim3(TGS_GROUP), 0, s, k, N, splats, group_base,
+                         sub_start, sc.rank, (uint2*)sc.pairs, status);
+      TGS_CHECK_LAUNCH();
+    }
     // The long-list classes are launched only if the caller's bound on the frame's longest list allows such lists
     // (max_list_hint < 0: no bound, every class): an unused class launch returns at once but still costs ~4.6 us of
     // the stream (profiles/r4_b_reconcile.json: 9.3 us per step at cfg3 for two launches that never had a list).
     const bool want_wg4 = max_list_hint < 0 || max_list_hint > 1024;
     const bool want_huge = max_list_hint < 0 || max_list_hint > 4096;
-    const int sorted_up_to = want_huge ? 0x7fffffff : (want_wg4 ? 4096 : 1024);
+    const int class_up_to = want_huge ? 0x7fffffff : (want_wg4 ? 4096 : 1024);
+    const int sorted_up_to = bins ? min(class_up_to, bin_cap) : class_up_to;
     const int wave_up_to = want_wg4 ? 512 : 1024;
-    hipLaunchKernelGGL(k_sort_tiles_wave, dim3(T + n_order), dim3(TGS_WAVE), 0, s, T, tile_start,
-                       sc.pairs, sorted_gid, tile_order, n_order, chunk, sorted_up_to, status, sticky_overflow, wave_up_to);
+    if (bins)
+      hipLaunchKernelGGL(k_sort_tiles_wave<true>, dim3(T + n_order), dim3(TGS_WAVE), 0, s, T, tile_start, (const u64*)bins,
+                         sorted_gid, tile_order, n_order, chunk, sorted_up_to, status, sticky_overflow, wave_up_to, max_list,
+                         sub_start, bin_cap);
+    else
+      hipLaunchKernelGGL(k_sort_tiles_wave<false>, dim3(T + n_order), dim3(TGS_WAVE), 0, s, T, tile_start, sc.pairs,
+                         sorted_gid, tile_order, n_order, chunk, sorted_up_to, status, sticky_overflow, wave_up_to, max_list,
+                         sub_start, 0);
     TGS_CHECK_LAUNCH();
     if (want_wg4) {
-      hipLaunchKernelGGL(k_sort_tiles_wg4, dim3(T < 2048 ? T : 2048), dim3(TGS_WAVE * 4), 0, s, T, tile_start,
-                         sc.pairs, sorted_gid, max_list, wave_up_to);
+      const int hi = min(sorted_up_to, 4096);
+      if (bins)
+        hipLaunchKernelGGL(k_sort_tiles_wg4<true>, dim3(T < 2048 ? T : 2048), dim3(TGS_WAVE * 4), 0, s, T, tile_start,
+                           (const u64*)bins, sorted_gid, max_list, wave_up_to, hi, sub_start, bin_cap);
+      else
+        hipLaunchKernelGGL(k_sort_tiles_wg4<false>, dim3(T < 2048 ? T : 2048), dim3(TGS_WAVE * 4), 0, s, T, tile_start,
+                           sc.pairs, sorted_gid, max_list, wave_up_to, hi, sub_start, 0);
       TGS_CHECK_LAUNCH();
     }
     if (want_huge) {
@@ -631,10 +692,37 @@ int tgs_bin_finish(const CamK& k, int N, const float* splats, const int32_t* gro
   return TGS_OK;
 }
 
+extern "C" int64_t tgs_bins_len(int T, int cap) { return (T > 0 && cap > 0) ? tgs_bins_entries(T, cap) : 0; }
+
+// bins == NULL: tgs_bin_sort.  Else tgs_bin_sort_bins: the same frame through the direct bins -- count into the bins, scan, sort.
+static int bin_sort_impl(const TgsCamera* cam, int N, float* splats, int32_t* group_base,
+                         int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
+                         int32_t* tile_order, int64_t capacity, void* scratch, int32_t* status,
+                         int32_t* sticky_overflow, int32_t max_list_hint, void* bins, int64_t bins_len, int32_t cap,
+                         bool with_bins, void* stream);
+
 extern "C" int tgs_bin_sort(const TgsCamera* cam, int N, float* splats, int32_t* group_base,
                             int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
                             int32_t* tile_order, int64_t capacity, void* scratch, int32_t* status,
                             int32_t* sticky_overflow, int32_t max_list_hint, void* stream) {
+  return bin_sort_impl(cam, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid, tile_order, capacity,
+                       scratch, status, sticky_overflow, max_list_hint, nullptr, 0, 0, false, stream);
+}
+
+extern "C" int tgs_bin_sort_bins(const TgsCamera* cam, int N, float* splats, int32_t* group_base,
+                                 int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
+                                 int32_t* tile_order, int64_t capacity, void* scratch, int32_t* status,
+                                 int32_t* sticky_overflow, int32_t max_list_hint, void* bins, int64_t bins_len, int32_t cap,
+                                 void* stream) {
+  return bin_sort_impl(cam, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid, tile_order, capacity,
+                       scratch, status, sticky_overflow, max_list_hint, bins, bins_len, cap, true, stream);
+}
+
+static int bin_sort_impl(const TgsCamera* cam, int N, float* splats, int32_t* group_base,
+                         int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
+                         int32_t* tile_order, int64_t capacity, void* scratch, int32_t* status,
+                         int32_t* sticky_overflow, int32_t max_list_hint, void* bins, int64_t bins_len, int32_t cap,
+                         bool with_bins, void* stream) {
   TGS_CHECK_ARG(camera_ok(cam), "bad camera");
   TGS_CHECK_ARG(N >= 0 && capacity >= 0, "negative size");
   TGS_CHECK_ARG(capacity < (1ll << 31), "capacity must be < 2^31");
@@ -644,6 +732,8 @@ extern "C" int tgs_bin_sort(const TgsCamera* cam, int N, float* splats, int32_t*
   const CamK k = make_camk(cam);
   const int T = k.TW * k.TH;
   TGS_CHECK_ARG(tile_start_len >= (int64_t)T + 1 + TGS_TILE_START_SCRATCH, "tile_start buffer shorter than tgs_tile_start_len(W, H)");
+  TGS_CHECK_ARG(!with_bins || (bins && cap >= 1 && cap <= 4096 && bins_len >= tgs_bins_len(T, cap)),
+                "bins must be non-null, cap in [1, 4096] and bins_len >= tgs_bins_len(T, cap)");
   const int G = tgs_num_groups(N);
   hipStream_t s = (hipStream_t)stream;
   const BinScratch sc = carve_scratch(scratch, capacity);
@@ -651,10 +741,15 @@ extern "C" int tgs_bin_sort(const TgsCamera* cam, int N, float* splats, int32_t*
                      sticky_overflow);
   TGS_CHECK_LAUNCH();
   if (G > 0) {
-    hipLaunchKernelGGL(k_tile_count, dim3(G), dim3(TGS_GROUP), 0, s, k, N, splats, group_base,
-                       tile_cursor, sc.rank, status, (long long)capacity, sticky_overflow);
+    if (with_bins)
+      hipLaunchKernelGGL(k_tile_count<true>, dim3(G), dim3(TGS_GROUP), 0, s, k, N, splats, group_base,
+                         tile_cursor, sc.rank, status, (long long)capacity, sticky_overflow, (uint2*)bins, (int)cap);
+    else
+      hipLaunchKernelGGL(k_tile_count<false>, dim3(G), dim3(TGS_GROUP), 0, s, k, N, splats, group_base,
+                         tile_cursor, sc.rank, status, (long long)capacity, sticky_overflow, (uint2*)nullptr, 0);
     TGS_CHECK_LAUNCH();
   }
   return tgs_bin_finish(k, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid, tile_order,
-                        capacity, scratch, status, sticky_overflow, max_list_hint, nullptr, s);
+                        capacity, scratch, status, sticky_overflow, max_list_hint, nullptr, s,
+                        with_bins ? (const uint2*)bins : nullptr, with_bins ? (int)cap : 0);
 }

@@ -129,6 +129,8 @@ struct NextFront {
   int32_t* status;
   long long capacity;
   int32_t* sticky;
+  uint2* bins;     // direct bins of the next frame (tgs_binning.h), or nullptr: ranks into `rank`, k_fill_bins scatters
+  int bin_cap;
 };
 
 struct NextView {
@@ -294,12 +296,14 @@ __device__ __forceinline__ float sigmoid_deriv(float x) {
 // project_fwd_core: everything after the parameters and the colour are in registers (m, ls, q, opac_logit value,
 // rgb; ignored for g >= N) -- shared by the stand-alone K1 below and by the fused K8 + Adam kernel, which runs
 // the NEXT view's K1 on the parameters it has just updated (front prefetch).
-template <bool FUSED>
+// BINS (FUSED only): the counting stores every pair in the direct bins (tgs_binning.h) instead of remembering its rank.
+template <bool FUSED, bool BINS = false>
 __device__ __forceinline__ void project_fwd_core(
     const CamK& cam, int N, int g, const float* m, const float* ls, const float* q, float ol, const float* rgb,
     float* __restrict__ splats, int32_t* __restrict__ radii, int32_t* __restrict__ group_base,
     int32_t* __restrict__ tile_count, int32_t* __restrict__ rank, int32_t* __restrict__ status,
-    long long capacity, int32_t* __restrict__ sticky, GroupScan* Sp) {
+    long long capacity, int32_t* __restrict__ sticky, GroupScan* Sp, uint2* __restrict__ bins = nullptr,
+    int bin_cap = 0) {
   unsigned rect = 0u;
   float tz = 0.f, c1 = 0.f, c2 = 0.f;
   if (g < N) {
@@ -361,7 +365,8 @@ __device__ __forceinline__ void project_fwd_core(
       float* o = splats + (size_t)g * TGS_SPLAT_FLOATS;
       st4(o + 8, make_float4(c1, c2, __uint_as_float(rect), __int_as_float(my_off)));
     }
-    group_count_tiles(S, cam.TW, cam.TW * cam.TH, total, group_base, tile_count, rank, status, capacity, sticky, cam.long_run);
+    group_count_tiles<BINS>(S, cam.TW, cam.TW * cam.TH, total, group_base, tile_count, rank, status, capacity, sticky,
+                            cam.long_run, bins, bin_cap);
   }
 }
 
@@ -1021,7 +1026,9 @@ __global__ __launch_bounds__(256) void k_pose_grad_final(int G, const float* __r
 // DEG is the ACTIVE SH degree, KS the number of bases each Gaussian STORES (KS >= (DEG+1)^2, 3*KS a
 // multiple of 4): while the trainer ramps the degree up, the rows above the active degree receive a
 // zero gradient (and, fused, a plain Adam step on it).
-template <int DEG, int KS, bool FUSE_ADAM, bool COLOR_ONLY = false>
+// BINS (FUSE_ADAM): the front prefetch's K1 bins its pairs directly (nx.fr.bins).  An instantiation of its own: the form without
+// bins keeps its instruction stream (with both countings behind a branch in one kernel the fill path lost 3 us per cfg3 step).
+template <int DEG, int KS, bool FUSE_ADAM, bool COLOR_ONLY = false, bool BINS = false>
 __global__ __launch_bounds__(256) void k_project_bwd_lds(
     CamK cam, int N, float* __restrict__ means, float* __restrict__ log_scales,
     float* __restrict__ quats, float* __restrict__ opac_logit, float* __restrict__ sh,
@@ -1118,9 +1125,9 @@ __global__ __launch_bounds__(256) void k_project_bwd_lds(
         // evaluated) as the stand-alone kernel would read back from memory -> bit-identical records and counts.
         // The group scan takes over the (consumed) SH image.
         __syncthreads();
-        project_fwd_core<true>(nx.fr.cam, N, g, m, ls, q, ol, rgb, nx.fr.splats, nx.fr.radii, nx.fr.group_base,
+        project_fwd_core<true, BINS>(nx.fr.cam, N, g, m, ls, q, ol, rgb, nx.fr.splats, nx.fr.radii, nx.fr.group_base,
                                nx.fr.tile_count, nx.fr.rank, nx.fr.status, nx.fr.capacity, nx.fr.sticky,
-                               reinterpret_cast<GroupScan*>(lds4));
+                               reinterpret_cast<GroupScan*>(lds4), nx.fr.bins, nx.fr.bin_cap);
       }
       if (g == 0) *nx.tag = nx.tag_value;
     }
@@ -1455,8 +1462,15 @@ static int project_bwd_adam_impl(const TgsCamera* cam, int N, int sh_stride, int
                      p.log_scales, p.quats, p.opac, p.sh, splats, group_base, partials,          \
                      (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,         \
                      (float*)nullptr, v_xy, a, exp_avg, exp_avg_sq, nx)
-  DISPATCH_DEG_KS(LAUNCH_F, sh_deg, sh_stride);
+#define LAUNCH_FB(D, KS)                                                                                      \
+  hipLaunchKernelGGL((k_project_bwd_lds<D, KS, true, false, true>), grid, block, lds_bytes, s, k, N, p.means, \
+                     p.log_scales, p.quats, p.opac, p.sh, splats, group_base, partials,                       \
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,                      \
+                     (float*)nullptr, v_xy, a, exp_avg, exp_avg_sq, nx)
+  if (nx.fr.splats && nx.fr.bins) DISPATCH_DEG_KS(LAUNCH_FB, sh_deg, sh_stride);
+  else DISPATCH_DEG_KS(LAUNCH_F, sh_deg, sh_stride);
 #undef LAUNCH_F
+#undef LAUNCH_FB
   TGS_CHECK_LAUNCH();
   return TGS_OK;
 }
@@ -1495,6 +1509,7 @@ static int next_front_begin(const char* fn, const TgsCamera* next_cam, float* sp
   fr->splats = splats_next; fr->radii = radii_next; fr->group_base = group_base_next;
   fr->tile_count = tile_cursor_next; fr->rank = carve_scratch(scratch_next, capacity_next).rank;
   fr->status = status_next; fr->capacity = (long long)capacity_next; fr->sticky = sticky_overflow;
+  fr->bins = nullptr; fr->bin_cap = 0;
   if (!counters_cleared) {
     const int T = fr->cam.TW * fr->cam.TH;
     hipLaunchKernelGGL(k_clear_counters, dim3((max(TGS_XCC * T, 2) + 255) / 256), dim3(256), 0, s, tile_cursor_next, T,
@@ -1511,7 +1526,50 @@ static int next_front_begin(const char* fn, const TgsCamera* next_cam, float* sp
 #define NEXT_FRONT_ARGS(fr) \
   (fr).splats, (fr).radii, (fr).group_base, (fr).tile_count, (fr).rank, (fr).status, (fr).capacity, (fr).sticky
 
+// The direct bins of a W x H frame as the two _bins entry points take them: cap in [1, 4096] (the register sorts' classes; the
+// `huge` class keeps the fill path) and at least tgs_bins_len entries.  Checked before any launch.
+static int bins_ok(const char* fn, const TgsCamera* cam, const void* bins, int64_t bins_len, int32_t cap) {
+  const CamK k = make_camk(cam);
+  if (!bins || cap < 1 || cap > 4096 || bins_len < tgs_bins_len(k.TW * k.TH, cap)) {
+    tgs_set_error("%s: bins must be non-null, cap in [1, 4096] and bins_len >= tgs_bins_len(T, cap) (got cap %d, bins_len %lld, need %lld)",
+                  fn, (int)cap, (long long)bins_len, (long long)tgs_bins_len(k.TW * k.TH, cap > 0 ? cap : 0));
+    return TGS_E_ARG;
+  }
+  return TGS_OK;
+}
+
 // Fused K8 + Adam + the next view's colours AND its K1 (front prefetch); tgs_project_bin_sort_front finishes that frame.
+// bins != NULL (checked by the caller): that K1 stores its pairs in the direct bins, tgs_project_bin_sort_front_bins finishes.
+static int project_bwd_adam_next_front_impl(const char* fn, const TgsCamera* cam, int N, int sh_stride, int sh_deg,
+                                            float* params, float* exp_avg, float* exp_avg_sq,
+                                            const TgsAdamSpec* spec, const float* splats,
+                                            const int32_t* group_base, const float* partials,
+                                            float* v_xy, const int32_t* skip_if_overflow,
+                                            const TgsCamera* next_cam, float* colors_next,
+                                            int32_t* tag_word, int32_t tag_value,
+                                            float* splats_next, int32_t* radii_next,
+                                            int32_t* group_base_next, int32_t* tile_cursor_next,
+                                            int64_t capacity_next, void* scratch_next,
+                                            int32_t* status_next, int32_t* sticky_overflow,
+                                            int counters_cleared, void* bins, int32_t cap, void* stream) {
+  if (N <= 0) return TGS_OK;
+  NextFront fr;
+  if (const int rc = next_front_begin(fn, next_cam, splats_next, radii_next, group_base_next, tile_cursor_next,
+                                      capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared,
+                                      (hipStream_t)stream, &fr)) return rc;
+  fr.bins = (uint2*)bins; fr.bin_cap = bins ? cap : 0;
+  NextView nx = next_view(fr.cam, colors_next, tag_word, tag_value);
+  nx.fr = fr;
+  return project_bwd_adam_impl(cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
+                               group_base, partials, v_xy, skip_if_overflow, nx, stream);
+}
+#define NEXT_FRONT_CHECKS()                                                                                              \
+  TGS_CHECK_ARG(camera_ok(next_cam), "bad next camera");                                                                 \
+  TGS_CHECK_ARG(next_cam->W <= 4080 && next_cam->H <= 4080, "image side > 4080 px (255 tiles)");                          \
+  TGS_CHECK_ARG(colors_next && tag_word, "null colour prefetch buffer");                                                 \
+  TGS_CHECK_ARG(splats_next && group_base_next && tile_cursor_next && scratch_next && status_next, "null front buffer"); \
+  TGS_CHECK_ARG(capacity_next >= 0 && capacity_next < (1ll << 31), "bad capacity")
+
 extern "C" int tgs_project_bwd_adam_next_front(const TgsCamera* cam, int N, int sh_stride, int sh_deg,
                                                float* params, float* exp_avg, float* exp_avg_sq,
                                                const TgsAdamSpec* spec, const float* splats,
@@ -1524,21 +1582,36 @@ extern "C" int tgs_project_bwd_adam_next_front(const TgsCamera* cam, int N, int 
                                                int64_t capacity_next, void* scratch_next,
                                                int32_t* status_next, int32_t* sticky_overflow,
                                                int counters_cleared, void* stream) {
-  TGS_CHECK_ARG(camera_ok(next_cam), "bad next camera");
-  TGS_CHECK_ARG(next_cam->W <= 4080 && next_cam->H <= 4080, "image side > 4080 px (255 tiles)");
-  TGS_CHECK_ARG(colors_next && tag_word, "null colour prefetch buffer");
-  TGS_CHECK_ARG(splats_next && group_base_next && tile_cursor_next && scratch_next && status_next, "null front buffer");
-  TGS_CHECK_ARG(capacity_next >= 0 && capacity_next < (1ll << 31), "bad capacity");
-  if (N <= 0) return TGS_OK;
-  NextFront fr;
-  if (const int rc = next_front_begin(__func__, next_cam, splats_next, radii_next, group_base_next, tile_cursor_next,
-                                      capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared,
-                                      (hipStream_t)stream, &fr)) return rc;
-  NextView nx = next_view(fr.cam, colors_next, tag_word, tag_value);
-  nx.fr = fr;
-  return project_bwd_adam_impl(cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
-                               group_base, partials, v_xy, skip_if_overflow, nx, stream);
+  NEXT_FRONT_CHECKS();
+  return project_bwd_adam_next_front_impl(__func__, cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
+                                          group_base, partials, v_xy, skip_if_overflow, next_cam, colors_next, tag_word,
+                                          tag_value, splats_next, radii_next, group_base_next, tile_cursor_next,
+                                          capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared,
+                                          nullptr, 0, stream);
 }
+
+extern "C" int tgs_project_bwd_adam_next_front_bins(const TgsCamera* cam, int N, int sh_stride, int sh_deg,
+                                                    float* params, float* exp_avg, float* exp_avg_sq,
+                                                    const TgsAdamSpec* spec, const float* splats,
+                                                    const int32_t* group_base, const float* partials,
+                                                    float* v_xy, const int32_t* skip_if_overflow,
+                                                    const TgsCamera* next_cam, float* colors_next,
+                                                    int32_t* tag_word, int32_t tag_value,
+                                                    float* splats_next, int32_t* radii_next,
+                                                    int32_t* group_base_next, int32_t* tile_cursor_next,
+                                                    int64_t capacity_next, void* scratch_next,
+                                                    int32_t* status_next, int32_t* sticky_overflow,
+                                                    int counters_cleared, void* bins, int64_t bins_len, int32_t cap,
+                                                    void* stream) {
+  NEXT_FRONT_CHECKS();
+  if (const int rc = bins_ok(__func__, next_cam, bins, bins_len, cap)) return rc;
+  return project_bwd_adam_next_front_impl(__func__, cam, N, sh_stride, sh_deg, params, exp_avg, exp_avg_sq, spec, splats,
+                                          group_base, partials, v_xy, skip_if_overflow, next_cam, colors_next, tag_word,
+                                          tag_value, splats_next, radii_next, group_base_next, tile_cursor_next,
+                                          capacity_next, scratch_next, status_next, sticky_overflow, counters_cleared,
+                                          bins, cap, stream);
+}
+#undef NEXT_FRONT_CHECKS
 
 // Data-parallel counterpart: geometry Adam from the all-reduced gradients + the next view's K1 (see the kernel).
 extern "C" int tgs_adam_geom_project_next(const TgsCamera* next_cam, int N, int sh_stride, int sh_deg,
@@ -1586,6 +1659,29 @@ extern "C" int tgs_front_can_clear_next(int N, int W, int H) {
 // If the tag does not match (the fused kernel was voided by its overflow guard, which also left the sticky word raised)
 // the scan launch voids the frame: empty lists, status[1] = 1 (binning.hip, ScanFront) -- no K1 is re-run for a frame
 // nobody will look at.  The caller replays through tgs_project_bin_sort once it has dealt with the overflow.
+static int project_bin_sort_front_impl(const TgsCamera* cam, int N, float* splats, int32_t* group_base,
+                                       int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
+                                       int32_t* tile_order, int64_t capacity, void* scratch,
+                                       int32_t* status, int32_t* sticky_overflow, int32_t max_list_hint,
+                                       const int32_t* tag_word, int32_t tag_expect,
+                                       const TgsCamera* next_cam, int32_t* next_tile_cursor,
+                                       int32_t* next_status, const void* bins, int32_t cap, void* stream) {
+  BinFront front;
+  front.tag_word = tag_word; front.tag_expect = tag_expect;
+  front.next_tile_cursor = next_tile_cursor; front.next_status = next_status; front.next_T = 0;
+  if (next_tile_cursor) {
+    TGS_CHECK_ARG(camera_ok(next_cam) && next_status, "next frame's counters without its camera / status word");
+    const CamK kn = make_camk(next_cam);
+    front.next_T = kn.TW * kn.TH;
+  }
+  TGS_CHECK_ARG(group_base && tile_start && tile_cursor && sorted_gid && scratch && status && tag_word, "null pointer");
+  TGS_CHECK_ARG(splats, "null pointer");
+  const CamK k = make_camk(cam);
+  return tgs_bin_finish(k, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid, tile_order,
+                        capacity, scratch, status, sticky_overflow, max_list_hint, &front, (hipStream_t)stream,
+                        (const uint2*)bins, bins ? cap : 0);
+}
+
 extern "C" int tgs_project_bin_sort_front(const TgsCamera* cam, int N, const float* means,
                                           const float* log_scales, const float* quats,
                                           const float* opac_logit, const float* sh, int sh_stride,
@@ -1598,20 +1694,32 @@ extern "C" int tgs_project_bin_sort_front(const TgsCamera* cam, int N, const flo
                                           int32_t* next_status, void* stream) {
   TGS_CHECK_ARG(camera_ok(cam), "bad camera");
   TGS_CHECK_ARG(N > 0 && capacity >= 0 && capacity < (1ll << 31), "bad size");
-  BinFront front;
-  front.tag_word = tag_word; front.tag_expect = tag_expect;
-  front.next_tile_cursor = next_tile_cursor; front.next_status = next_status; front.next_T = 0;
-  if (next_tile_cursor) {
-    TGS_CHECK_ARG(camera_ok(next_cam) && next_status, "next frame's counters without its camera / status word");
-    const CamK kn = make_camk(next_cam);
-    front.next_T = kn.TW * kn.TH;
-  }
-  TGS_CHECK_ARG(group_base && tile_start && tile_cursor && sorted_gid && scratch && status && tag_word, "null pointer");
-  TGS_CHECK_ARG(splats, "null pointer");
   (void)means; (void)log_scales; (void)quats; (void)opac_logit; (void)sh; (void)sh_stride; (void)sh_deg; (void)radii;
-  const CamK k = make_camk(cam);
-  return tgs_bin_finish(k, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid, tile_order,
-                        capacity, scratch, status, sticky_overflow, max_list_hint, &front, (hipStream_t)stream);
+  return project_bin_sort_front_impl(cam, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid,
+                                     tile_order, capacity, scratch, status, sticky_overflow, max_list_hint, tag_word,
+                                     tag_expect, next_cam, next_tile_cursor, next_status, nullptr, 0, stream);
+}
+
+// ... of a frame whose K1 tgs_project_bwd_adam_next_front_bins ran (same bins, same cap): scan and sort only, the sorts gather
+// each list from the tile's 8 sub-bins.  A list longer than `cap` voids the frame, whatever max_list_hint says.
+extern "C" int tgs_project_bin_sort_front_bins(const TgsCamera* cam, int N, const float* means,
+                                               const float* log_scales, const float* quats,
+                                               const float* opac_logit, const float* sh, int sh_stride,
+                                               int sh_deg, float* splats, int32_t* radii, int32_t* group_base,
+                                               int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor,
+                                               int32_t* sorted_gid, int32_t* tile_order, int64_t capacity, void* scratch,
+                                               int32_t* status, int32_t* sticky_overflow, int32_t max_list_hint,
+                                               const int32_t* tag_word, int32_t tag_expect,
+                                               const TgsCamera* next_cam, int32_t* next_tile_cursor,
+                                               int32_t* next_status, const void* bins, int64_t bins_len, int32_t cap,
+                                               void* stream) {
+  TGS_CHECK_ARG(camera_ok(cam), "bad camera");
+  TGS_CHECK_ARG(N > 0 && capacity >= 0 && capacity < (1ll << 31), "bad size");
+  if (const int rc = bins_ok(__func__, cam, bins, bins_len, cap)) return rc;
+  (void)means; (void)log_scales; (void)quats; (void)opac_logit; (void)sh; (void)sh_stride; (void)sh_deg; (void)radii;
+  return project_bin_sort_front_impl(cam, N, splats, group_base, tile_start, tile_start_len, tile_cursor, sorted_gid,
+                                     tile_order, capacity, scratch, status, sticky_overflow, max_list_hint, tag_word,
+                                     tag_expect, next_cam, next_tile_cursor, next_status, bins, cap, stream);
 }
 
 // K1 + K3a fused, then scan / fill / sort: the whole front half of a frame in one call.

@@ -27,10 +27,13 @@ struct BinFront {
   int32_t* next_status;
   int next_T;
 };
+// `bins` != NULL (bin_cap entries per (XCC, tile), tgs_bins_entries): this frame's K1 stored its pairs there (group_count_tiles<true>)
+// -- no fill launch, the sorts gather from the bins, and a list longer than bin_cap voids the frame.
 int tgs_bin_finish(const CamK& k, int N, const float* splats, const int32_t* group_base,
                    int32_t* tile_start, int64_t tile_start_len, int32_t* tile_cursor, int32_t* sorted_gid,
                    int32_t* tile_order, int64_t capacity, void* scratch, int32_t* status,
-                   int32_t* sticky_overflow, int32_t max_list_hint, const BinFront* front, hipStream_t s);
+                   int32_t* sticky_overflow, int32_t max_list_hint, const BinFront* front, hipStream_t s,
+                   const uint2* bins = nullptr, int bin_cap = 0);
 
 // Per-tile intersection counters are kept once per XCD (row x of an [8][T] array, x = the XCC the
 // counting workgroup runs on): the 8 L2s of an MI355X are kept coherent by ownership migration, so a
@@ -225,15 +228,25 @@ __device__ __forceinline__ void group_pairs_xy(const GroupScan& S, int i0, int s
   }
 }
 
+// Direct bins (front prefetch with a list bound): bins[(xcc * T + tile) * cap + rank] = {gid, depth bits}.  When K1 counts a
+// pair it knows everything about it except where its tile's list starts -- which is all k_fill_bins adds, in a pass of
+// its own over the records.  A fixed-capacity bin per (XCC, tile) needs no start: K1 stores the pair at its arrival rank
+// and the sort kernels gather a tile's list from its 8 sub-bins (binning.hip, PairSrc).  `cap` is the caller's bound on
+// the longest LIST (max_list_hint): a sub-list is never longer than its list, and a list beyond the bound voids the frame
+// anyway.  A rank >= cap drops the pair and voids the frame here.
+static inline int64_t tgs_bins_entries(int T, int cap) { return (int64_t)TGS_XCC * T * cap; }
+
 // Allocates the group's contiguous pair range and counts its intersections per tile; every pair
-// remembers its arrival rank inside its tile.  Call after group_scan_store + __syncthreads-free
-// (this function synchronises internally).
+// remembers its arrival rank inside its tile (BINS: is stored at that rank in its (XCC, tile) bin instead, and `rank`
+// is not written).  Call after group_scan_store + __syncthreads-free (this function synchronises internally).
+template <bool BINS = false>
 __device__ __forceinline__ void group_count_tiles(GroupScan& S, int TW, int T, int total,
                                                   int32_t* __restrict__ group_base,
                                                   int32_t* __restrict__ tile_count,
                                                   int32_t* __restrict__ rank,
                                                   int32_t* __restrict__ status, long long capacity,
-                                                  int32_t* __restrict__ sticky, int long_run) {
+                                                  int32_t* __restrict__ sticky, int long_run,
+                                                  uint2* __restrict__ bins = nullptr, int bin_cap = 0) {
   const int tid = threadIdx.x;
   const int x = xcc_id();
   // pair range of the group: one returning atomic on the XCD's allocator.  Issued first and consumed
@@ -264,6 +277,8 @@ __device__ __forceinline__ void group_count_tiles(GroupScan& S, int TW, int T, i
     for (int b = tid; b < area; b += TGS_GROUP) S.hist[b] = 0;
   __syncthreads();                                            // the group scan (and the cleared histogram) is visible
   int lr[TGS_AGG_U], lb[TGS_AGG_U];
+  int lj[BINS ? TGS_AGG_U : 1], lt[BINS ? TGS_AGG_U : 1];   // BINS: the pair's Gaussian and tile live on to the store
+  bool bin_full = false;
   if (agg) {
     {
       int j[TGS_AGG_U], tx[TGS_AGG_U], ty[TGS_AGG_U];
@@ -274,6 +289,7 @@ __device__ __forceinline__ void group_count_tiles(GroupScan& S, int TW, int T, i
 #pragma unroll
       for (int u = 0; u < TGS_AGG_U; u++) {
         lb[u] = -1; lr[u] = 0;
+        if constexpr (BINS) { lj[u] = j[u]; lt[u] = ty[u] * TW + tx[u]; }
         if (valid[u]) {
           if (lng[u]) {                                         // a long run's pair: counted directly (outside the box)
             lb[u] = -2;
@@ -333,12 +349,22 @@ __device__ __forceinline__ void group_count_tiles(GroupScan& S, int TW, int T, i
   __syncthreads();
   const long long base = S.base;
   const bool fits = S.fits != 0;
+  const int g0 = tgs_group_id() * TGS_GROUP;
+  uint2* __restrict__ my_bins = BINS ? bins + (size_t)x * T * bin_cap : nullptr;
   int first_direct = 0;
   if (agg) {
 #pragma unroll
     for (int u = 0; u < TGS_AGG_U; u++) {
       const int i = tid + u * TGS_GROUP;
-      if (lb[u] != -1 && fits) rank[base + i] = (int32_t)((unsigned)((lb[u] >= 0 ? S.hist[lb[u]] : 0) + lr[u]) | ((unsigned)x << 29));
+      if (lb[u] != -1 && fits) {
+        const unsigned r = (unsigned)((lb[u] >= 0 ? S.hist[lb[u]] : 0) + lr[u]);
+        if constexpr (BINS) {
+          if (r < (unsigned)bin_cap) my_bins[(size_t)lt[u] * bin_cap + r] = make_uint2((unsigned)(g0 + lj[u]), S.depth_bits[lj[u]]);
+          else bin_full = true;
+        } else {
+          rank[base + i] = (int32_t)(r | ((unsigned)x << 29));
+        }
+      }
     }
     first_direct = TGS_AGG_U * TGS_GROUP;                     // pairs beyond 1024 per group (huge footprints)
   }
@@ -347,19 +373,34 @@ __device__ __forceinline__ void group_count_tiles(GroupScan& S, int TW, int T, i
   // object-centric 720p frame: 2.6 k), and one returning atomic per round made its ~110 dependent round trips the
   // duration of the whole launch (K1 + count 104 us for 79 k Gaussians, profiles/r6_before_*).
   for (int i0 = tid + first_direct; i0 < total; i0 += TGS_DIRECT_U * TGS_GROUP) {
-    int tile[TGS_DIRECT_U], r[TGS_DIRECT_U];
+    int tile[TGS_DIRECT_U], r[TGS_DIRECT_U], dj[BINS ? TGS_DIRECT_U : 1];
     {
       int j[TGS_DIRECT_U], tx[TGS_DIRECT_U], ty[TGS_DIRECT_U];
       bool valid[TGS_DIRECT_U];
       group_pairs_xy<TGS_DIRECT_U>(S, i0, TGS_GROUP, total, j, tx, ty, valid);
 #pragma unroll
-      for (int u = 0; u < TGS_DIRECT_U; u++) tile[u] = valid[u] ? ty[u] * TW + tx[u] : -1;
+      for (int u = 0; u < TGS_DIRECT_U; u++) {
+        tile[u] = valid[u] ? ty[u] * TW + tx[u] : -1;
+        if constexpr (BINS) dj[u] = j[u];
+      }
     }
 #pragma unroll
     for (int u = 0; u < TGS_DIRECT_U; u++) r[u] = tile[u] >= 0 ? atomicAdd(&my_count[tile[u]], 1) : 0;
 #pragma unroll
-    for (int u = 0; u < TGS_DIRECT_U; u++)   // rank inside sub-list x of the tile (capacity < 2^29 pairs per sub-list)
-      if (tile[u] >= 0 && fits) rank[base + i0 + u * TGS_GROUP] = (int32_t)((unsigned)r[u] | ((unsigned)x << 29));
+    for (int u = 0; u < TGS_DIRECT_U; u++) {   // rank inside sub-list x of the tile (capacity < 2^29 pairs per sub-list)
+      if (tile[u] >= 0 && fits) {
+        if constexpr (BINS) {
+          if ((unsigned)r[u] < (unsigned)bin_cap) my_bins[(size_t)tile[u] * bin_cap + r[u]] = make_uint2((unsigned)(g0 + dj[u]), S.depth_bits[dj[u]]);
+          else bin_full = true;
+        } else {
+          rank[base + i0 + u * TGS_GROUP] = (int32_t)((unsigned)r[u] | ((unsigned)x << 29));
+        }
+      }
+    }
+  }
+  if (BINS && bin_full) {   // a sub-list outgrew the caller's list bound: the frame is void, as the sort would have made it
+    status[1] = 1;
+    if (sticky) *sticky = 1;
   }
 }
 #endif  // __HIPCC__

@@ -234,6 +234,9 @@ class DepthGaussianSplattingModel:
         self.dp_factored_sh = True   # data-parallel steps exchange colour gradients, not SH rows
         # single-process steps that know the next view: its K1 runs inside this step's optimizer kernel
         self.front_prefetch = os.environ.get("TGS_FRONT_PREFETCH", "1") != "0"
+        # ... and, with a list bound on the budget, bins its pairs directly (ops.set_front_bins / TGS_FRONT_BINS is the process-wide
+        # switch and ceiling; this is the model's own)
+        self.front_bins = True
         self.last = {}
         self.tuning = Tuning()      # until the first re-sort that has seen a frame: the process defaults
         self._tuned_cams = {}
@@ -1033,6 +1036,10 @@ class DepthGaussianSplattingModel:
         front = None
         if self.front_prefetch and not (fuse and torch.cuda.is_current_stream_capturing()):
             front = ops.FrontBuffers(next_cam, N, self.budget.initial(N), self.density is not None, dev)
+            # direct bins (fused single-process step only): sized by the budget's list bound as it stands NOW -- the buffers
+            # are per frame, so the bins follow a hint the trainer re-learns; no bound, or bins over the ceiling: fill pass
+            if fuse and self.front_bins:
+                front.attach_bins(self.budget.list_hint())
         return (bufs[1] if in_use is bufs[0] else bufs[0]).arm(next_cam, deg, front, self.budget, colors_valid=fuse)
 
     def _factored_tail(self, dp, view: View, deg: int, arm) -> None:

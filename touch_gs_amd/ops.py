@@ -202,11 +202,31 @@ class ColorPrefetch:
 _SIDE_CLEAR = _os.environ.get("TGS_FRONT_SIDE_CLEAR", "1") != "0"   # A/B switch: next frame's counters cleared by extra workgroups of this frame's scan launch
 
 
+# Direct bins (tgs.h): the K1 inside the fused optimizer kernel stores every pair in a fixed-capacity bin of its
+# (XCC, tile) and the fill pass leaves the step (cfg3: -12 us per step for 534 MB of bins per frame in flight).
+# TGS_FRONT_BINS=0 / set_front_bins(False): off (A/B switch);
+# TGS_FRONT_BINS_MAX_MB: the most one frame's bins may take (8 * tiles * max_list_hint * 8 bytes), beyond it the frame keeps the fill pass.
+_FRONT_BINS = [_os.environ.get("TGS_FRONT_BINS", "1") != "0", int(_os.environ.get("TGS_FRONT_BINS_MAX_MB", "1024")) << 20]
+BINS_MAX_CAP = 4096    # the register sorts' classes; longer lists (`huge`) keep the fill pass
+
+
+def set_front_bins(on: Optional[bool] = None, max_bytes: Optional[int] = None):
+    """-> (on, ceiling in bytes) of the direct bins after applying the arguments (None = leave as it is)."""
+    if on is not None:
+        _FRONT_BINS[0] = bool(on)
+    if max_bytes is not None:
+        _FRONT_BINS[1] = max(int(max_bytes), 0)
+    return _FRONT_BINS[0], _FRONT_BINS[1]
+
+
 class FrontBuffers:
     """Everything the front half of ONE frame writes (what project_bin_sort allocates per call).  Allocated one
     step ahead when the previous step's fused optimizer kernel also runs this frame's K1 (front prefetch,
     tgs_project_bwd_adam_next_front): records, group bases, per-tile counters and ranks are then filled by that
-    kernel, and project_bin_sort only scans, fills and sorts (tgs_project_bin_sort_front)."""
+    kernel, and project_bin_sort only scans, fills and sorts (tgs_project_bin_sort_front) -- or, with ``bins``
+    (``attach_bins``), K1 stores the pairs there and project_bin_sort only scans and sorts (the _bins pair of calls)."""
+    bins, bin_cap = None, 0
+    bins_filled = False      # the optimizer call that ran this frame's K1 took the bins (optim.backward_and_step)
 
     def __init__(self, cam: Camera, N: int, cap: int, want_radii: bool, dev, records: bool = True):
         lib = _lib.load()
@@ -232,6 +252,20 @@ class FrontBuffers:
         self.cap = cap
         self.sorted_gid = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
         self.scratch = torch.empty(_lib.load().tgs_sort_scratch_bytes(cap), dtype=torch.uint8, device=dev)
+
+    def attach_bins(self, list_hint: int) -> bool:
+        """Direct bins for this frame, ``list_hint`` entries per (XCC, tile), if they are switched on, the hint is a
+        bound the register sorts cover and the bins fit the ceiling -> True.  Otherwise the frame keeps the fill pass."""
+        on, ceiling = _FRONT_BINS
+        T = self.cam.num_tiles
+        if not on or self.N <= 0 or not (0 < list_hint <= BINS_MAX_CAP):
+            return False
+        n = _lib.load().tgs_bins_len(T, int(list_hint))
+        if n * 8 > ceiling:
+            return False
+        self.bins = torch.empty(n, 2, dtype=torch.int32, device=self.group_base.device)   # {gid, depth bits}; never cleared
+        self.bin_cap = int(list_hint)
+        return True
 
     def settle(self, budget: IntersectBudget) -> bool:
         """After the front half was launched into these buffers: the frame's status words go to ``budget``; a synchronous
@@ -285,15 +319,19 @@ def project_bin_sort(cam: Camera, means, log_scales, quats, opac_logit, sh, sh_d
             nf = next_front if (_SIDE_CLEAR and next_front is not None and not next_front.cleared and next_front is not fb and
                                 lib.tgs_front_can_clear_next(N, next_front.cam.W, next_front.cam.H)) else None
             ncs = nf.cam.c_struct() if nf is not None else None
-            check(lib.tgs_project_bin_sort_front(C.byref(cs), N, ptr(means), ptr(log_scales), ptr(quats), ptr(opac_logit),
-                                                 ptr(sh), sh_stride, sh_deg, ptr(splats), ptr(radii), ptr(group_base),
-                                                 ptr(tile_start), _tile_start_len(tile_start), ptr(tile_cursor), ptr(sorted_gid),
-                                                 ptr(tile_order), cap, ptr(scratch), ptr(status), ptr(budget.sticky_word(dev)),
-                                                 budget.list_hint(), ptr(tag_holder.tag_word), tag_holder.tag,
-                                                 C.byref(ncs) if nf is not None else None,
-                                                 ptr(nf.tile_cursor) if nf is not None else None,
-                                                 ptr(nf.status) if nf is not None else None, _stream()),
-                  "tgs_project_bin_sort_front")
+            front_args = (C.byref(cs), N, ptr(means), ptr(log_scales), ptr(quats), ptr(opac_logit),
+                          ptr(sh), sh_stride, sh_deg, ptr(splats), ptr(radii), ptr(group_base),
+                          ptr(tile_start), _tile_start_len(tile_start), ptr(tile_cursor), ptr(sorted_gid),
+                          ptr(tile_order), cap, ptr(scratch), ptr(status), ptr(budget.sticky_word(dev)),
+                          budget.list_hint(), ptr(tag_holder.tag_word), tag_holder.tag,
+                          C.byref(ncs) if nf is not None else None,
+                          ptr(nf.tile_cursor) if nf is not None else None,
+                          ptr(nf.status) if nf is not None else None)
+            if fb.bins_filled:           # the K1 that filled these buffers stored its pairs in the bins: no ranks to fill from
+                check(lib.tgs_project_bin_sort_front_bins(*front_args, ptr(fb.bins), fb.bins.shape[0], fb.bin_cap, _stream()),
+                      "tgs_project_bin_sort_front_bins")
+            else:
+                check(lib.tgs_project_bin_sort_front(*front_args, _stream()), "tgs_project_bin_sort_front")
             if nf is not None:
                 nf.cleared = True
             from_front = False          # a regrown capacity (synchronous budget) goes through the regular K1
