@@ -15,7 +15,8 @@
 // bank-conflict cycles; 77 + 80 us at 1080p).  Read amplification here: 74/64 horizontally,
 // (SEG+10)/SEG vertically.  Roofline: HBM (9 adjoint planes written, then read).
 // From 1080p on a gradient call runs k_ssim_fused instead (below): both filters in one pass over the same strips, the adjoint
-// values in a two-row LDS ring instead of HBM, every output bit-identical (ssim_impl).
+// values in a two-row LDS ring instead of HBM.  The filter arithmetic of all three kernels is the shared device functions
+// below (one copy of each body), which is what keeps every output bit-identical between them (ssim_impl).
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -24,28 +25,14 @@
 namespace {
 
 constexpr int WIN = 11, HALO = 5;
-struct Win { float g[WIN]; };
 // The window weights as compile-time constants (11-tap Gaussian, sigma 1.5, normalised in double and rounded
-// to fp32 -- the values the host used to pass as a kernel argument).  As kernel arguments they sat in SGPRs,
-// and on gfx950 a VALU instruction with an SGPR source is the most expensive form there is (v_mul / v_add
-// 5.45 cycles, v_fma 4.5 - 5.5, against 2.8 - 3.0 with a literal: tools/ubench/valu_cost.hip) -- every FMA
-// of the two filters is of that kind.  TGS_SSIM_SGPR_WINDOW restores the argument form for A/B runs.
-#ifdef TGS_SSIM_SGPR_WINDOW
-#define WK(k) win.g[k]
-#else
+// to fp32).  As kernel arguments they would sit in SGPRs, and on gfx950 a VALU instruction with an SGPR source
+// is the most expensive form there is (v_mul / v_add 5.45 cycles, v_fma 4.5 - 5.5, against 2.8 - 3.0 with a
+// literal: tools/ubench/valu_cost.hip) -- every FMA of the two filters is of that kind.
 __device__ constexpr float WGT[WIN] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f, 0x1.b43c4p-3f,
                                        0x1.10656p-2f, 0x1.b43c4p-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f,
                                        0x1.0d956cp-10f};
-#define WK(k) WGT[k]
-#endif
 
-// TGS_SSIM_DMA (bit 0: k_ssim_fwd, bit 1: k_ssim_bwd): the staged rows are brought in by LDS-DMA (`buffer_load_dword ... lds`: no
-// VGPRs, zero fill outside the image by the buffer's own range check) into one of TWO LDS images, and the next block's
-// rows are requested before the current block is filtered -- a request stays in flight across the barrier, so the
-// load -> barrier -> filter chain of a workgroup becomes max(load, filter) per block.
-#ifndef TGS_SSIM_DMA
-#define TGS_SSIM_DMA 0
-#endif
 constexpr int SW = 64;              // strip width (output columns per workgroup)
 constexpr int NTH = 3 * SW;         // threads: (column, channel)
 constexpr int RB = WIN;             // input rows per staged block = window height (phase p = row in block)
@@ -54,13 +41,19 @@ constexpr int RB = WIN;             // input rows per staged block = window heig
 // blocks of a segment, and an 800x800 image has only 312 segments of 34 rows for 256 CUs.
 __host__ __device__ constexpr int seg_rows(int nblk) { return RB * nblk - 2 * HALO; }
 
+// Loads in flight per thread and staging round:
+constexpr int FWD_B = 13;   // all 13 + 13 loads of a block in flight at once (round 5: 128 VGPRs, still 4 waves per SIMD); 7 = two rounds
+constexpr int BWD_B = 20;   // two rounds of 20 instead of three of 13 (66 VGPRs); all 39 at once spills.  Both: 99.4 -> 97.7 us (r5_ab_runs.txt)
+
 // Stages input rows [r0, r0 + RB) x columns [x0 - 5, x0 + SW + 5) of an interleaved [H, W, CH]
-// image into LDS (zero outside the image), in batches of 8 loads in flight per thread.
+// image into LDS (zero outside the image), in rounds of B loads in flight per thread.
+// stage and stage2 are one loop for one and for two images; as one template over the image count the forward kernel
+// spilled 26 registers and the backward kernel's register and VALU counts moved (profiles/ssim_shared_isa.txt).
 template <int CH>
 struct RowBlock {
   static constexpr int ROWF = (SW + 2 * HALO) * CH;             // floats per staged row
   static constexpr int NIT = (RB * ROWF + NTH - 1) / NTH;
-  template <int B = 8>
+  template <int B>
   static __device__ __forceinline__ void stage(const float* __restrict__ src, float* __restrict__ lds,
                                                int W, int H, int x0, int r0, int tid) {
 #pragma unroll 1
@@ -81,38 +74,13 @@ struct RowBlock {
       }
     }
   }
-  // LDS-DMA staging: wave w of the workgroup fills floats [64 w + NTH u, + 64) of the image in iteration u (one
-  // `buffer_load_dword ... lds` per wave and iteration: 64 lanes x 4 B land contiguously at M0 + 4 lane); an element
-  // outside the image gets an offset beyond the buffer and reads as zero.  PADF: the image rounded up to whole waves.
-  static constexpr int PADF = (RB * ROWF + TGS_WAVE - 1) / TGS_WAVE * TGS_WAVE;
-  static constexpr int NDMA = PADF / TGS_WAVE;                       // wave-chunks per staged block
-  static __device__ __forceinline__ void dma(__amdgpu_buffer_rsrc_t rsrc, float* __restrict__ lds, int W, int H, int x0, int r0, int tid) {
-    typedef __attribute__((address_space(3))) float lds_float;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    constexpr int NW = NTH / TGS_WAVE;
-    const int gx0 = (x0 - HALO) * CH, WC = W * CH;
-#pragma unroll
-    for (int u = 0; u * NW < NDMA; u++) {
-      const int chunk = u * NW + wave;                               // wave-uniform
-      if (chunk < NDMA) {
-        const int i = chunk * TGS_WAVE + lane;
-        const int j = i / ROWF, e = i - j * ROWF;                    // (constant divisor: a multiply)
-        const int gy = r0 + j, gxf = gx0 + e;
-        const bool in = i < RB * ROWF && (unsigned)gy < (unsigned)H && (unsigned)gxf < (unsigned)WC;
-        const unsigned off = in ? (unsigned)(gy * WC + gxf) * 4u : 0xffffffffu;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_float*)(lds + chunk * TGS_WAVE), 4, off, 0, 0, 0);
-      }
-    }
-  }
   // Two images of the same geometry in one pass: the loads of both are in flight together, which halves
-  // the number of load -> wait round trips per block (the forward kernel is a chain of them).
+  // the number of load -> wait round trips per block (the forward kernel is a chain of them; staging them one after
+  // the other in rounds of 8: forward + backward 118 -> 111 us at 1080p, same box).
+  template <int B>
   static __device__ __forceinline__ void stage2(const float* __restrict__ src_a, const float* __restrict__ src_b,
                                                 float* __restrict__ lds_a, float* __restrict__ lds_b,
                                                 int W, int H, int x0, int r0, int tid) {
-#ifndef TGS_SSIM_FWD_B
-#define TGS_SSIM_FWD_B 13   // all 13 + 13 loads of a block in flight at once (round 5: 128 VGPRs, still 4 waves per SIMD); 7 = two rounds
-#endif
-    constexpr int B = TGS_SSIM_FWD_B;
 #pragma unroll 1
     for (int it0 = 0; it0 < NIT; it0 += B) {
       float va[B], vb[B];
@@ -136,7 +104,91 @@ struct RowBlock {
   }
 };
 
-__global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_ssim_fwd(int W, int H, Win win,
+// ---------------------------------------------------------------------------------------------
+// The filter bodies: one copy each, used by k_ssim_fwd, k_ssim_bwd and k_ssim_fused
+// ---------------------------------------------------------------------------------------------
+// No floating-point operation here may change its order or its contraction: v_img is bit-identical between the
+// two-kernel path and the one-pass kernel, and block_partials between forms 0 and 2 (tests/test_gpu_ssim_one_pass.py).
+
+// Horizontal pass of one staged row of img (ra) and gt (rb) for this thread's (column, channel): the five moments.
+__device__ __forceinline__ void moments_row(const float* ra, const float* rb, float (&w)[5]) {
+  float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIN; k++) {
+    const float a = ra[3 * k], b = rb[3 * k];
+    const float ga = WGT[k] * a, gb = WGT[k] * b;
+    m1 += ga; m2 += gb;
+    e11 = fmaf(ga, a, e11); e22 = fmaf(gb, b, e22); e12 = fmaf(ga, b, e12);
+  }
+  w[0] = m1; w[1] = m2; w[2] = e11; w[3] = e22; w[4] = e12;
+}
+
+// Horizontal pass of one adjoint row ([column][channel][3 maps]) for this thread's (column, channel).
+__device__ __forceinline__ void adjoint_row(const float* r, float (&w)[3]) {
+  float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIN; k++) {
+    h0 = fmaf(WGT[k], r[9 * k], h0);
+    h1 = fmaf(WGT[k], r[9 * k + 1], h1);
+    h2 = fmaf(WGT[k], r[9 * k + 2], h2);
+  }
+  w[0] = h0; w[1] = h1; w[2] = h2;
+}
+
+// Vertical pass over the register window after row p of a block went in: slots (p+1 .. p+11) mod 11 = oldest .. newest.
+template <int Q>
+__device__ __forceinline__ void vertical(const float (&w)[RB][Q], int p, float (&o)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; q++) o[q] = 0.f;
+#pragma unroll
+  for (int k = 0; k < WIN; k++) {
+#pragma unroll
+    for (int q = 0; q < Q; q++) o[q] = fmaf(WGT[k], w[(p + 1 + k) % RB][q], o[q]);
+  }
+}
+
+// The SSIM value m of one (pixel, channel) from its five filtered moments, with what the adjoint needs of it.
+struct SsimPoint { float m, mu1, mu2, n1, n2, id1, id2; };
+__device__ __forceinline__ SsimPoint ssim_point(const float (&o)[5]) {
+  const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
+  const float mu1 = o[0], mu2 = o[1];
+  const float s11 = o[2] - mu1 * mu1, s22 = o[3] - mu2 * mu2, s12 = o[4] - mu1 * mu2;
+  const float n1 = 2.f * mu1 * mu2 + C1, n2 = 2.f * s12 + C2;
+  const float d1 = mu1 * mu1 + mu2 * mu2 + C1, d2 = s11 + s22 + C2;
+  // v_rcp_f32 (1 ulp) instead of the ~10-instruction IEEE division: d1, d2 >= C1, C2 > 0
+  const float id1 = __builtin_amdgcn_rcpf(d1), id2 = __builtin_amdgcn_rcpf(d2);
+  return {n1 * n2 * id1 * id2, mu1, mu2, n1, n2, id1, id2};
+}
+
+// A = dm/dmu1 (total), B = dm/dE[x^2], C = dm/dE[xy].  Apart from ssim_point: a forward-only call does not pay for it.
+__device__ __forceinline__ void ssim_adjoint(const SsimPoint& s, float& A, float& B, float& C) {
+  const float dm_ds12 = 2.f * s.n1 * s.id1 * s.id2;
+  const float dm_ds11 = -s.m * s.id2;
+  const float dm_dmu1 = 2.f * s.mu2 * s.n2 * s.id1 * s.id2 - s.m * 2.f * s.mu1 * s.id1;
+  A = dm_dmu1 - 2.f * s.mu1 * dm_ds11 - s.mu2 * dm_ds12;
+  B = dm_ds11;
+  C = dm_ds12;
+}
+
+// v_img of one (pixel, channel) from its three filtered adjoint maps; x = img, y = gt there.
+__device__ __forceinline__ float grad_value(float weight, const float (&o)[3], float x, float y) {
+  return weight * (o[0] + 2.f * x * o[1] + y * o[2]);
+}
+
+// Workgroup sum of the map -> block_partials[workgroup]; the caller's buffer has one entry per 16x16 tile: the entries
+// beyond the workgroup count are zeroed.  Three waves hold the sums (the fourth wave of k_ssim_fused holds no output column).
+template <int NT>
+__device__ __forceinline__ void store_block_sum(float v, float* __restrict__ block_partials, int n_partials, int tid) {
+  __shared__ float red[NT / TGS_WAVE];
+  const float tot = wave_sum(v);
+  if ((tid & 63) == 0) red[tid >> 6] = tot;
+  __syncthreads();
+  const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
+  if (tid == 0) block_partials[wg] = red[0] + red[1] + red[2];
+  for (int i = nwg + wg * NT + tid; i < n_partials; i += nwg * NT) block_partials[i] = 0.f;
+}
+
+__global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_ssim_fwd(int W, int H,
                                                   const float* __restrict__ img,
                                                   const float* __restrict__ gt,
                                                   float* __restrict__ adj /*[H,W,3,3] or null*/,
@@ -146,14 +198,7 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   // 5-row halo its backward pass needs); rows [c_lo, c_hi) count towards the sum
   const int SEG = seg_rows(NBLK);
   constexpr int ROWF = RowBlock<3>::ROWF;
-#if TGS_SSIM_DMA & 1
-  __shared__ float sa2[2][RowBlock<3>::PADF], sb2[2][RowBlock<3>::PADF];
-  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)img, 0, (int)((size_t)W * H * 12), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)gt, 0, (int)((size_t)W * H * 12), 0x00020000);
-#else
   __shared__ float sa[RB * ROWF], sb[RB * ROWF];
-#endif
-  __shared__ float red[NTH / TGS_WAVE];
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * SW, ys = y_lo + blockIdx.y * SEG;
   const int gx = x0 + tid / 3, c = tid - (tid / 3) * 3;
@@ -164,103 +209,43 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
     for (int q = 0; q < 5; q++) w[p][q] = 0.f;
   float msum = 0.f;
-#if TGS_SSIM_DMA & 1
-  RowBlock<3>::dma(rs_a, sa2[0], W, H, x0, ys - HALO, tid);
-  RowBlock<3>::dma(rs_b, sb2[0], W, H, x0, ys - HALO, tid);
-#endif
   for (int blk = 0; blk < NBLK; blk++) {
     const int r0 = ys - HALO + blk * RB;          // first input row of this block
     if (r0 - HALO >= ye) break;                   // no output row left (uniform)
-#if TGS_SSIM_DMA & 1
-    // this block's rows have landed (own requests: vmcnt; the other waves': the barrier) -- and every wave is done with
-    // the OTHER image, which the next block's requests overwrite while this block is filtered
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (blk + 1 < NBLK && r0 + RB - HALO < ye) {
-      RowBlock<3>::dma(rs_a, sa2[(blk + 1) & 1], W, H, x0, r0 + RB, tid);
-      RowBlock<3>::dma(rs_b, sb2[(blk + 1) & 1], W, H, x0, r0 + RB, tid);
-    }
-    const float* sa = sa2[blk & 1];
-    const float* sb = sb2[blk & 1];
-#else
     __syncthreads();                              // previous block fully consumed
-    {
-      // no register prefetch of the next block: the window already holds 55 VGPRs per thread and
-      // the other resident workgroups of the CU cover the load latency
-      // both images in one pass, NIT = 13: two rounds of 7 + 7 loads in flight (staging them one after
-      // the other in rounds of 8: forward + backward 118 -> 111 us at 1080p, same box)
-      RowBlock<3>::stage2(img, gt, sa, sb, W, H, x0, r0, tid);
-    }
+    // no register prefetch of the next block: the window already holds 55 VGPRs per thread and
+    // the other resident workgroups of the CU cover the load latency
+    RowBlock<3>::stage2<FWD_B>(img, gt, sa, sb, W, H, x0, r0, tid);
     __syncthreads();
-#endif
 #pragma unroll
     for (int p = 0; p < RB; p++) {
-      // horizontal pass of input row r0 + p for (column, channel) = this thread
-      const float* ra = sa + p * ROWF + tid;
-      const float* rb = sb + p * ROWF + tid;
-      float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; k++) {
-        const float a = ra[3 * k], b = rb[3 * k];
-        const float ga = WK(k) * a, gb = WK(k) * b;
-        m1 += ga; m2 += gb;
-        e11 = fmaf(ga, a, e11); e22 = fmaf(gb, b, e22); e12 = fmaf(ga, b, e12);
-      }
-      w[p][0] = m1; w[p][1] = m2; w[p][2] = e11; w[p][3] = e22; w[p][4] = e12;
-      // vertical pass: output row = r0 + p - 5; window slots (p+1 .. p+11) mod 11 = oldest .. newest
-      const int gy = r0 + p - HALO;
+      moments_row(sa + p * ROWF + tid, sb + p * ROWF + tid, w[p]);     // input row r0 + p
+      const int gy = r0 + p - HALO;               // output row
       if (gy >= ys && gy < ye) {                  // uniform
-        float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < WIN; k++) {
-#pragma unroll
-          for (int q = 0; q < 5; q++) o[q] = fmaf(WK(k), w[(p + 1 + k) % RB][q], o[q]);
-        }
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float mu1 = o[0], mu2 = o[1];
-        const float s11 = o[2] - mu1 * mu1, s22 = o[3] - mu2 * mu2, s12 = o[4] - mu1 * mu2;
-        const float n1 = 2.f * mu1 * mu2 + C1, n2 = 2.f * s12 + C2;
-        const float d1 = mu1 * mu1 + mu2 * mu2 + C1, d2 = s11 + s22 + C2;
-        // v_rcp_f32 (1 ulp) instead of the ~10-instruction IEEE division: d1, d2 >= C1, C2 > 0
-        const float id1 = __builtin_amdgcn_rcpf(d1), id2 = __builtin_amdgcn_rcpf(d2);
-        const float m = n1 * n2 * id1 * id2;
+        float o[5];
+        vertical(w, p, o);
+        const SsimPoint s = ssim_point(o);
         if (gx < W) {
-          if (gy >= c_lo && gy < c_hi) msum += m;
+          if (gy >= c_lo && gy < c_hi) msum += s.m;
           if (adj) {
-            const float dm_ds12 = 2.f * n1 * id1 * id2;
-            const float dm_ds11 = -m * id2;
-            const float dm_dmu1 = 2.f * mu2 * n2 * id1 * id2 - m * 2.f * mu1 * id1;
             float* o3 = adj + (((size_t)gy * W + gx) * 3 + c) * 3;
-            o3[0] = dm_dmu1 - 2.f * mu1 * dm_ds11 - mu2 * dm_ds12;
-            o3[1] = dm_ds11;
-            o3[2] = dm_ds12;
+            ssim_adjoint(s, o3[0], o3[1], o3[2]);
           }
         }
       }
     }
   }
-  const float tot = wave_sum(msum);
-  if ((tid & 63) == 0) red[tid >> 6] = tot;
-  __syncthreads();
-  const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
-  if (tid == 0) block_partials[wg] = red[0] + red[1] + red[2];
-  // the caller's buffer has one entry per 16x16 tile: the entries beyond the workgroup count are zero
-  for (int i = nwg + wg * NTH + tid; i < n_partials; i += nwg * NTH) block_partials[i] = 0.f;
+  store_block_sum<NTH>(msum, block_partials, n_partials, tid);
 }
 
-__global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_ssim_bwd(int W, int H, Win win, float weight,
+__global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_ssim_bwd(int W, int H, float weight,
                                                   const float* __restrict__ img,
                                                   const float* __restrict__ gt,
                                                   const float* __restrict__ adj,
                                                   float* __restrict__ v_img, int NBLK, int y_lo, int y_hi) {
   const int SEG = seg_rows(NBLK);
   constexpr int ROWF = RowBlock<9>::ROWF;
-#if TGS_SSIM_DMA & 2
-  __shared__ float sadj2[2][RowBlock<9>::PADF];
-  const __amdgpu_buffer_rsrc_t rs_j = __builtin_amdgcn_make_buffer_rsrc((void*)adj, 0, (int)((size_t)W * H * 36), 0x00020000);
-#else
   __shared__ float sadj[RB * ROWF];
-#endif
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * SW, ys = y_lo + blockIdx.y * SEG;
   const int gx = x0 + tid / 3;
@@ -268,51 +253,22 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   float w[RB][3];
 #pragma unroll
   for (int p = 0; p < RB; p++) { w[p][0] = 0.f; w[p][1] = 0.f; w[p][2] = 0.f; }
-#if TGS_SSIM_DMA & 2
-  RowBlock<9>::dma(rs_j, sadj2[0], W, H, x0, ys - HALO, tid);
-#endif
   for (int blk = 0; blk < NBLK; blk++) {
     const int r0 = ys - HALO + blk * RB;
     if (r0 - HALO >= ye) break;
-#if TGS_SSIM_DMA & 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (blk + 1 < NBLK && r0 + RB - HALO < ye) RowBlock<9>::dma(rs_j, sadj2[(blk + 1) & 1], W, H, x0, r0 + RB, tid);
-    const float* sadj = sadj2[blk & 1];
-#else
+    RowBlock<9>::stage<BWD_B>(adj, sadj, W, H, x0, r0, tid);      // 38 loads per thread and block
     __syncthreads();
-    {
-      // 38 loads per thread and block: three rounds of 13 in flight (the kernel has registers to spare)
-#ifndef TGS_SSIM_BWD_B
-#define TGS_SSIM_BWD_B 20   // two rounds of 20 instead of three of 13 (66 VGPRs); all 39 at once spills.  Both: 99.4 -> 97.7 us (r5_ab_runs.txt)
-#endif
-      RowBlock<9>::stage<TGS_SSIM_BWD_B>(adj, sadj, W, H, x0, r0, tid);
-    }
-    __syncthreads();
-#endif
 #pragma unroll
     for (int p = 0; p < RB; p++) {
-      const float* r = sadj + p * ROWF + 3 * tid;     // (pixel, channel) -> its three adjoint maps
-      float h0 = 0.f, h1 = 0.f, h2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < WIN; k++) {
-        h0 = fmaf(WK(k), r[9 * k], h0);
-        h1 = fmaf(WK(k), r[9 * k + 1], h1);
-        h2 = fmaf(WK(k), r[9 * k + 2], h2);
-      }
-      w[p][0] = h0; w[p][1] = h1; w[p][2] = h2;
+      adjoint_row(sadj + p * ROWF + 3 * tid, w[p]);   // (pixel, channel) -> its three adjoint maps
       const int gy = r0 + p - HALO;
       if (gy >= ys && gy < ye) {
-        float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; k++) {
-          o0 = fmaf(WK(k), w[(p + 1 + k) % RB][0], o0);
-          o1 = fmaf(WK(k), w[(p + 1 + k) % RB][1], o1);
-          o2 = fmaf(WK(k), w[(p + 1 + k) % RB][2], o2);
-        }
+        float o[3];
+        vertical(w, p, o);
         if (gx < W) {
           const size_t pidx = (size_t)gy * W * 3 + (size_t)x0 * 3 + tid;
-          v_img[pidx] = weight * (o0 + 2.f * img[pidx] * o1 + gt[pidx] * o2);
+          v_img[pidx] = grad_value(weight, o, img[pidx], gt[pidx]);
         }
       }
     }
@@ -328,12 +284,12 @@ __global__ __launch_bounds__(NTH) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // Here a workgroup owns SWO output columns x SEG rows and keeps everything between the two filters on chip.  Its 256
 // threads are (column, channel) pairs: the first 3 (SWO + 10) of them run phase 1 on the strip's adjoint columns
 // [x0 - 5, x0 + SWO + 5), the first 3 SWO run phase 2 on its output columns.  Per staged input row r (11 to a block):
-//   phase 1  = k_ssim_fwd's loop body verbatim: horizontal moments from LDS, the last 11 rows in registers, SSIM map +
-//              the three adjoint values of (row r - 5, own column) -> LDS (zero outside the image: the backward
-//              filter's zero padding);
+//   phase 1  = k_ssim_fwd's loop body, the shared functions: horizontal moments from LDS, the last 11 rows in registers,
+//              SSIM map + the three adjoint values of (row r - 5, own column) -> LDS (zero outside the image: the
+//              backward filter's zero padding);
 //   barrier
-//   phase 2  = k_ssim_bwd's loop body verbatim on that ONE adjoint row: horizontal filter of the three adjoint maps from
-//              LDS, the last 11 rows in registers, v_img of row r - 10.
+//   phase 2  = k_ssim_bwd's loop body, the shared functions, on that ONE adjoint row: horizontal filter of the three
+//              adjoint maps from LDS, the last 11 rows in registers, v_img of row r - 10.
 // The backward's vertical window lives in registers, so only the row in flight has to be in LDS: a ring of two rows
 // (phase 1 fills one while slower waves still read the other; one barrier per row) in place of the 11 rows x 64 x 9
 // floats of the first one-pass kernel -- 27 KB of LDS instead of 45, 4 waves per SIMD instead of 2.
@@ -361,7 +317,6 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   static_assert(ROWF <= FT && NT1 <= FT && FT <= RB * ROWF, "one staged float, one adjoint (column, channel) per thread");
   __shared__ float sa[RB * ROWF], sb[RB * ROWF];
   __shared__ float sadj[2 * ADJF];
-  __shared__ float red[FT / TGS_WAVE];
   const int tid = threadIdx.x;
   const unsigned ut = tid;                           // index of a global access: uniform base + 32-bit lane offset
   const int col = tid / 3;
@@ -406,41 +361,16 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       const int gyo = r0 + p - 2 * HALO;              // phase 2: output row
       // ---- phase 1: moments -> SSIM map -> adjoint values of row r0 + p - 5 at column gxa
       if (tid < NT1) {
-        const float* ra = sa + p * ROWF + tid;
-        const float* rb = sb + p * ROWF + tid;
-        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; k++) {
-          const float a = ra[3 * k], b = rb[3 * k];
-          const float ga = WK(k) * a, gb = WK(k) * b;
-          m1 += ga; m2 += gb;
-          e11 = fmaf(ga, a, e11); e22 = fmaf(gb, b, e22); e12 = fmaf(ga, b, e12);
-        }
-        w[p][0] = m1; w[p][1] = m2; w[p][2] = e11; w[p][3] = e22; w[p][4] = e12;
+        moments_row(sa + p * ROWF + tid, sb + p * ROWF + tid, w[p]);
         const int gy = r0 + p - HALO;                // map / adjoint row
         float A = 0.f, B = 0.f, C = 0.f;
         if (gy >= ys - HALO && gy < ye + HALO && gy >= 0 && gy < H) {      // uniform
-          float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int k = 0; k < WIN; k++) {
-#pragma unroll
-            for (int q = 0; q < 5; q++) o[q] = fmaf(WK(k), w[(p + 1 + k) % RB][q], o[q]);
-          }
-          const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-          const float mu1 = o[0], mu2 = o[1];
-          const float s11 = o[2] - mu1 * mu1, s22 = o[3] - mu2 * mu2, s12 = o[4] - mu1 * mu2;
-          const float n1 = 2.f * mu1 * mu2 + C1, n2 = 2.f * s12 + C2;
-          const float d1 = mu1 * mu1 + mu2 * mu2 + C1, d2 = s11 + s22 + C2;
-          const float id1 = __builtin_amdgcn_rcpf(d1), id2 = __builtin_amdgcn_rcpf(d2);
-          const float m = n1 * n2 * id1 * id2;
+          float o[5];
+          vertical(w, p, o);
+          const SsimPoint s = ssim_point(o);
           if (adj_in) {
-            if (own_col && gy >= ys && gy < ye && gy >= c_lo && gy < c_hi) msum += m;
-            const float dm_ds12 = 2.f * n1 * id1 * id2;
-            const float dm_ds11 = -m * id2;
-            const float dm_dmu1 = 2.f * mu2 * n2 * id1 * id2 - m * 2.f * mu1 * id1;
-            A = dm_dmu1 - 2.f * mu1 * dm_ds11 - mu2 * dm_ds12;
-            B = dm_ds11;
-            C = dm_ds12;
+            if (own_col && gy >= ys && gy < ye && gy >= c_lo && gy < c_hi) msum += s.m;
+            ssim_adjoint(s, A, B, C);
           }
         }
         float* o3 = sadj + (p & 1) * ADJF + tid * 3;
@@ -449,26 +379,13 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
       __syncthreads();                               // the row is in LDS; every wave is done with the row before the last
       // ---- phase 2: filtered adjoint maps -> v_img of row r0 + p - 10 at column gxo (adjoint columns col .. col + 10)
       if (tid < NT2) {
-        const float* r = sadj + (p & 1) * ADJF + tid * 3;
-        float h0 = 0.f, h1 = 0.f, h2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; k++) {
-          h0 = fmaf(WK(k), r[9 * k], h0);
-          h1 = fmaf(WK(k), r[9 * k + 1], h1);
-          h2 = fmaf(WK(k), r[9 * k + 2], h2);
-        }
-        w2[p][0] = h0; w2[p][1] = h1; w2[p][2] = h2;
+        adjoint_row(sadj + (p & 1) * ADJF + tid * 3, w2[p]);
         if (gyo >= ys && gyo < ye) {                 // uniform
-          float o0 = 0.f, o1 = 0.f, o2 = 0.f;
-#pragma unroll
-          for (int k = 0; k < WIN; k++) {
-            o0 = fmaf(WK(k), w2[(p + 1 + k) % RB][0], o0);
-            o1 = fmaf(WK(k), w2[(p + 1 + k) % RB][1], o1);
-            o2 = fmaf(WK(k), w2[(p + 1 + k) % RB][2], o2);
-          }
+          float o[3];
+          vertical(w2, p, o);
           if (out_in) {
             const ptrdiff_t orow = (ptrdiff_t)gyo * W * 3 + (ptrdiff_t)x0 * 3;     // uniform
-            (v_img + orow)[ut] = weight * (o0 + 2.f * (img + orow)[ut] * o1 + (gt + orow)[ut] * o2);
+            (v_img + orow)[ut] = grad_value(weight, o, (img + orow)[ut], (gt + orow)[ut]);
           }
         }
       }
@@ -478,12 +395,7 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(4, 8))) void
   __syncthreads();
   sa[tid] = msum;
   __syncthreads();
-  const float tot = wave_sum(tid < NT2 ? sa[tid + 3 * HALO] : 0.f);
-  if ((tid & 63) == 0) red[tid >> 6] = tot;
-  __syncthreads();
-  const int wg = blockIdx.y * gridDim.x + blockIdx.x, nwg = gridDim.x * gridDim.y;
-  if (tid == 0) block_partials[wg] = red[0] + red[1] + red[2];   // (the fourth wave holds no output column)
-  for (int i = nwg + wg * FT + tid; i < n_partials; i += nwg * FT) block_partials[i] = 0.f;
+  store_block_sum<FT>(tid < NT2 ? sa[tid + 3 * HALO] : 0.f, block_partials, n_partials, tid);
 }
 
 // No forward row to produce (an empty band): nothing counts, but the caller still sums block_partials.  A kernel rather
@@ -516,10 +428,6 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
   TGS_CHECK_ARG(img && gt && block_partials, "null pointer");
   TGS_CHECK_ARG(!v_img || scratch, "gradient needs scratch");
   TGS_CHECK_ARG(0 <= y0 && y0 <= y1 && y1 <= H && y0 <= c0 && c0 <= c1 && c1 <= y1, "bad row range");
-  Win win;
-  double g[WIN], sum = 0.0;
-  for (int i = 0; i < WIN; i++) { g[i] = exp(-(double)((i - HALO) * (i - HALO)) / (2.0 * 1.5 * 1.5)); sum += g[i]; }
-  for (int i = 0; i < WIN; i++) win.g[i] = (float)(g[i] / sum);
   static const int env_nblk = [] { const char* e = getenv("TGS_SSIM_NBLK"); return e ? max(2, min(16, atoi(e))) : 0; }();
   int form = g_ssim_form.get();
   if (form == SSIM_AUTO) form = (long long)W * H >= SSIM_ONE_PASS_MIN_PIXELS ? SSIM_ONE_PASS : SSIM_TWO_KERNELS;
@@ -554,12 +462,13 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
     return TGS_OK;
   }
   const int sx = (W + SW - 1) / SW;
+  auto wgs = [&](int nb) { return (long long)sx * ((rows + seg_rows(nb) - 1) / seg_rows(nb)); };
   int nblk = 4;
-  while (nblk > 2 && (long long)sx * ((rows + seg_rows(nblk) - 1) / seg_rows(nblk)) < 3 * 256) nblk--;
+  while (nblk > 2 && wgs(nblk) < 3 * 256) nblk--;
   if (env_nblk) nblk = env_nblk;   // tuning override (read once, above)
   // one workgroup sum goes into each of the first entries of block_partials, the rest is zeroed
-  while (nblk < 16 && (long long)sx * ((rows + seg_rows(nblk) - 1) / seg_rows(nblk)) > n_partials) nblk++;
-  TGS_CHECK_ARG((long long)sx * ((rows + seg_rows(nblk) - 1) / seg_rows(nblk)) <= n_partials, "block_partials too small");
+  while (nblk < 16 && wgs(nblk) > n_partials) nblk++;
+  TGS_CHECK_ARG(wgs(nblk) <= n_partials, "block_partials too small");
   const int SEG = seg_rows(nblk);
   const dim3 block(NTH);
   hipStream_t s = (hipStream_t)stream;
@@ -571,11 +480,11 @@ static int ssim_impl(int W, int H, const float* img, const float* gt, float weig
     TGS_CHECK_LAUNCH();
     return TGS_OK;
   }
-  hipLaunchKernelGGL(k_ssim_fwd, dim3(sx, (rows + SEG - 1) / SEG, 1), block, 0, s, W, H, win, img, gt,
+  hipLaunchKernelGGL(k_ssim_fwd, dim3(sx, (rows + SEG - 1) / SEG, 1), block, 0, s, W, H, img, gt,
                      v_img ? scratch : nullptr, block_partials, n_partials, nblk, f0, f1, c0, c1);
   TGS_CHECK_LAUNCH();
   if (v_img && y1 > y0) {
-    hipLaunchKernelGGL(k_ssim_bwd, dim3(sx, (y1 - y0 + SEG - 1) / SEG, 1), block, 0, s, W, H, win, weight, img, gt,
+    hipLaunchKernelGGL(k_ssim_bwd, dim3(sx, (y1 - y0 + SEG - 1) / SEG, 1), block, 0, s, W, H, weight, img, gt,
                        scratch, v_img, nblk, y0, y1);
     TGS_CHECK_LAUNCH();
   }
