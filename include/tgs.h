@@ -917,6 +917,39 @@ int tgs_tsdf_mesh_emit(int nx, int ny, int nz, float vox, const float* S, const 
                        int64_t* edge_key /*may be NULL*/, int32_t* faces, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Exact k nearest neighbours of 3-D points (csrc/knn.hip): the counterpart of the INRIA trainer's
+ * simple_knn.distCUDA2 (touch_gs_amd.simple_knn), the initial scales of touch_gs_amd.train.init_params(knn="hip") and the
+ * Chamfer / F-score of touch_gs_amd.tsdf.surface_metrics(device=...).  Additions within 320.  The library allocates nothing,
+ * never syncs and uses no atomics; between the calls the CALLER finds the bounds and sorts the keys (touch_gs_amd.ops.knn:
+ * amin / amax and one torch.sort).
+ * DEFINITION.  d2(q, r) = (dx*dx + dy*dy) + dz*dz with dx = qx - rx, dy = qy - ry, dz = qz - rz, every operation rounded to
+ *      fp32 on its own (no fused multiply-add).  Row q of dist2 holds the k smallest d2 over the eligible references in ascending
+ *      order, equal d2 ordered by the lower ORIGINAL reference index; idx holds the original indices.  With fewer than k
+ *      eligible references the trailing slots are +inf / -1.  So the result depends on neither the sort, the box size nor the
+ *      launch shape, and repeats bit for bit.  Non-finite coordinates are the caller's to refuse (a NaN distance never enters).
+ * tgs_knn_keys: keys[i] = the 30-bit Morton key of point i quantised to 1024^3 inside [lo, hi] (HOST floats [3]; bit 3 j + a =
+ *      bit j of axis a's cell).  Points outside are clamped; an axis with hi == lo quantises to 0 (nothing is divided by zero).
+ * tgs_knn_build: order [n] int32 = a permutation that sorts the keys (any permutation gives the same neighbours, a sorted one
+ *      gives the speed); sorted_pts [n,4] = {x, y, z, original index bits} in that order; boxes [ceil(n / TGS_KNN_BOX), 8] =
+ *      {min x y z, 0, max x y z, 0} of each run of TGS_KNN_BOX consecutive sorted points.
+ * tgs_knn_query: thread t serves query q_order[t] (int32 [n_q], a permutation; NULL = t), so that the 64 lanes of a wave are
+ *      spatial neighbours; rows of dist2 / idx [n_q,k] are the queries' own.  exclude_self != 0: the queries ARE the
+ *      references in their ORIGINAL order (n_q == n_ref) and the reference whose original index equals the query's index is
+ *      skipped -- by index, not by distance: duplicates of a point are its neighbours at distance 0.
+ * Every argument is checked before any launch (TGS_E_ARG: n, n_q, n_ref < 1 or > 2^29 - 1; k outside 1 .. TGS_KNN_MAX_K; null
+ * pointers; non-finite or inverted lo / hi; exclude_self with n_q != n_ref).  Equality with the brute-force reference:
+ * tests/test_gpu_knn.py. */
+#define TGS_KNN_MAX_K 16
+#define TGS_KNN_BOX   256      /* reference points per box: one 4 KB LDS stage of a wave, four per lane; DESIGN 5.1p */
+int tgs_knn_keys(int n, const float* pts /*[n,3]*/, const float* lo /*[host][3]*/, const float* hi /*[host][3]*/,
+                 uint32_t* keys /*[n]*/, void* stream);
+int tgs_knn_build(int n, const float* pts /*[n,3]*/, const int32_t* order /*[n]*/, float* sorted_pts /*[n,4]*/,
+                  float* boxes /*[ceil(n/TGS_KNN_BOX),8]*/, void* stream);
+int tgs_knn_query(int n_q, const float* queries /*[n_q,3]*/, const int32_t* q_order /*[n_q], may be NULL*/, int n_ref,
+                  const float* sorted_pts, const float* boxes, int k, int exclude_self, float* dist2 /*[n_q,k]*/,
+                  int32_t* idx /*[n_q,k]*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects
  * with TGS_DP_TRANSPORT=ipc (csrc/peer.hip).  The reference has no counterpart (single GPU).

@@ -18,6 +18,8 @@ EXPO_OUT = 32     # TGS_EXPO_OUT: floats of tgs_exposure_bwd's result and of a r
 EXPO_STATE = 48   # TGS_EXPO_STATE: floats of one view's exposure row (E | exp_avg | exp_avg_sq | t, beta1^t, beta2^t | 0...)
 EXPO_CHUNK = 2048  # pixels per workgroup of k_expo_bwd_tiles (csrc/exposure.hip): tgs_exposure_num_partials = ceil(W H / it)
 BLOCK = 16
+KNN_MAX_K = 16    # TGS_KNN_MAX_K
+KNN_BOX = 256     # TGS_KNN_BOX: reference points per box of tgs_knn_build
 
 
 class TgsCamera(C.Structure):
@@ -155,6 +157,9 @@ SIGNATURES = {
     "tgs_tsdf_extract_points": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     "tgs_tsdf_mesh_count": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, C.c_float, _P, _P, _P, _P]),
     "tgs_tsdf_mesh_emit": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tgs_knn_keys": (C.c_int, [_I, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "tgs_knn_build": (C.c_int, [_I, _P, _P, _P, _P, _P]),
+    "tgs_knn_query": (C.c_int, [_I, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "tgs_peer_alloc": (C.c_int, [C.c_size_t, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "tgs_peer_open": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_void_p)]),
     "tgs_peer_close": (C.c_int, [_P]),

@@ -101,9 +101,11 @@ def gt_surface_points(root: str, max_points: int = 400000) -> np.ndarray:
 
 def export_tsdf(run_dir: str, output_dir: str, resolution: int = 256, voxel_size=None, bounds=None, depth: str = "median",
                 weight: str = "inverse_variance", views: str = "train", device="cuda", w_min: float = 0.5,
-                loaded=None, mesh: bool = False) -> dict:
+                loaded=None, mesh: bool = False, metrics_device=None) -> dict:
     """-> what export.json holds.  ``loaded`` = a (model, cfg, scene) of :func:`load_run`, to spare the reload.  ``mesh``:
-    also write mesh.ply and add the ``mesh`` block (tsdf.mesh_stats in the capture's frame, and the seconds)."""
+    also write mesh.ply and add the ``mesh`` block (tsdf.mesh_stats in the capture's frame, and the seconds).
+    ``metrics_device``: where the Chamfer / F-score's nearest neighbours are found -- None = scipy on the host, a GPU device =
+    the HIP k-NN (tsdf.surface_metrics); recorded in the options."""
     import torch
     clock = time.perf_counter
     t0 = clock()
@@ -145,7 +147,9 @@ def export_tsdf(run_dir: str, output_dir: str, resolution: int = 256, voxel_size
     if os.path.isdir(os.path.join(scene.root, "gt_depth")):
         gt = gt_surface_points(scene.root)
         if len(gt):
-            info["surface_metrics"] = surface_metrics(pts, gt, tau=2 * vox_m)
+            info["surface_metrics"] = surface_metrics(pts, gt, tau=2 * vox_m, device=metrics_device)
+            if metrics_device is not None:
+                info["options"]["metrics_device"] = str(metrics_device)
             info["seconds"]["metrics"] = round(clock() - t4, 3)
     with open(os.path.join(output_dir, "export.json"), "w") as f:
         json.dump(info, f, indent=2)
@@ -201,10 +205,13 @@ def main(argv=None):
     t.add_argument("--weight", choices=("inverse_variance", "uniform"), default="inverse_variance")
     t.add_argument("--views", choices=("train", "all"), default="train")
     t.add_argument("--mesh", action="store_true", help="also write mesh.ply: the level set as a triangle mesh")
+    t.add_argument("--metrics-device", "--metrics_device", dest="metrics_device", default=None,
+                   help="find the surface metrics' nearest neighbours with the HIP k-NN on this device (e.g. cuda); "
+                        "default: scipy cKDTree on the host")
     a = ap.parse_args(argv)
     if a.what == "tsdf":
         info = export_tsdf(a.run, a.output_dir, a.resolution, a.voxel_size, a.bounds, a.depth, a.weight, a.views, a.device,
-                           mesh=a.mesh)
+                           mesh=a.mesh, metrics_device=a.metrics_device)
     else:
         info = export_gaussians(a.run, a.output_dir, a.device)
     print(json.dumps(info))

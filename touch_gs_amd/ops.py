@@ -1362,3 +1362,91 @@ def mcmc_relocate(ratio, opac_logit, log_scales, min_opacity: float = 0.005) -> 
     xc = x.clamp(min=lo, max=1.0 - 2.0 ** -23)
     opac_logit[sel] = (torch.log(xc) - torch.log1p(-xc)).float()
     log_scales[sel] = (log_scales[sel].double() + torch.log(o / S)[:, None]).float()
+
+
+# ------------------------------------------------------------------------------------------------
+# exact k nearest neighbours (csrc/knn.hip)
+# ------------------------------------------------------------------------------------------------
+def _knn_points(t, what: str):
+    if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == 3 and t.shape[0] >= 1):
+        raise ValueError(f"knn: {what} must be a [n, 3] tensor with n >= 1")
+    if t.dtype != torch.float32:
+        raise ValueError(f"knn: {what} must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        raise RuntimeError("touch_gs_amd ops need device (HIP) tensors; there is no CPU path")
+    if t.shape[0] > (1 << 29) - 1:
+        raise ValueError(f"knn: {what} holds more points than the 32-bit index (2^29 - 1)")
+    return t.detach().contiguous()
+
+
+def _knn_bounds(t, what: str):
+    """(lo, hi) of a [n,3] device tensor as host floats -- ONE host read; NaN and inf both surface in amin / amax."""
+    b = torch.stack([t.amin(0), t.amax(0)]).cpu()
+    if not bool(torch.isfinite(b).all()):
+        raise ValueError(f"knn: {what} holds non-finite coordinates")
+    return (C.c_float * 3)(*b[0].tolist()), (C.c_float * 3)(*b[1].tolist())
+
+
+def _knn_keys(lib, t, lo, hi):
+    """The points' 30-bit Morton keys inside [lo, hi] (int32: the sign bit stays clear)."""
+    keys = torch.empty(t.shape[0], dtype=torch.int32, device=t.device)
+    check(lib.tgs_knn_keys(t.shape[0], ptr(t), lo, hi, ptr(keys), _stream()), "tgs_knn_keys")
+    return keys
+
+
+def knn(points, k: int, queries=None, exclude_self: Optional[bool] = None, sort_queries: bool = True,
+        timing: Optional[dict] = None):
+    """The ``k`` nearest ``points`` (float32 [n,3] on the device, the references) of every query: ``(dist2 [n_q,k] float32,
+    idx [n_q,k] int32)`` on the device, exact -- d2 = (dx*dx + dy*dy) + dz*dz in fp32, each row ascending, equal d2 by the
+    lower index, ``+inf`` / ``-1`` where fewer than k references exist (include/tgs.h).  ``queries=None``: the points
+    themselves, each without itself (``exclude_self`` defaults to True then, to False with ``queries``; True needs the
+    queries to be the points in their order).  1 <= k <= 16.  Non-finite coordinates raise ValueError.  One host read per
+    cloud (the bounds); this is an initialisation / evaluation op, not a per-step one.
+    ``sort_queries=False`` serves the queries in their own order instead of Morton order (same result, slower: the lanes of
+    a wave then want different boxes).  ``timing``: a dict that receives a device event after each stage -- start, bounds,
+    keys, sort, build, query (tools/knn_time.py)."""
+    lib = _lib.load()
+    if not (isinstance(k, int) and 1 <= k <= _lib.KNN_MAX_K):
+        raise ValueError(f"knn: k must be an int in [1, {_lib.KNN_MAX_K}], got {k!r}")
+    ref = _knn_points(points, "points")
+    n = ref.shape[0]
+    self_query = queries is None
+    qs = ref if self_query else _knn_points(queries, "queries")
+    if qs.device != ref.device:
+        raise ValueError("knn: points and queries must be on one device")
+    if exclude_self is None:
+        exclude_self = self_query
+    if exclude_self and qs.shape[0] != n:
+        raise ValueError("knn: exclude_self needs the queries to be the points themselves (same count and order)")
+
+    def mark(name):
+        if timing is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            timing[name] = ev
+
+    with torch.cuda.device(ref.device):
+        mark("start")
+        lo, hi = _knn_bounds(ref, "points")
+        if not self_query:
+            _knn_bounds(qs, "queries")      # (refuses non-finite queries; their keys are clamped into the references' bounds)
+        mark("bounds")
+        keys = _knn_keys(lib, ref, lo, hi)
+        q_keys = _knn_keys(lib, qs, lo, hi) if (sort_queries and not self_query) else None
+        mark("keys")
+        order = torch.sort(keys).indices.to(torch.int32)
+        q_order = None
+        if sort_queries:
+            q_order = order if self_query else torch.sort(q_keys).indices.to(torch.int32)
+        mark("sort")
+        sorted_pts = torch.empty(n, 4, dtype=torch.float32, device=ref.device)
+        boxes = torch.empty((n + _lib.KNN_BOX - 1) // _lib.KNN_BOX, 8, dtype=torch.float32, device=ref.device)
+        check(lib.tgs_knn_build(n, ptr(ref), ptr(order), ptr(sorted_pts), ptr(boxes), _stream()), "tgs_knn_build")
+        mark("build")
+        n_q = qs.shape[0]
+        dist2 = torch.empty(n_q, k, dtype=torch.float32, device=ref.device)
+        idx = torch.empty(n_q, k, dtype=torch.int32, device=ref.device)
+        check(lib.tgs_knn_query(n_q, ptr(qs), ptr(q_order), n, ptr(sorted_pts), ptr(boxes), k, int(bool(exclude_self)),
+                                ptr(dist2), ptr(idx), _stream()), "tgs_knn_query")
+        mark("query")
+    return dist2, idx

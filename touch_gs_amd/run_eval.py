@@ -40,14 +40,15 @@ def load_model(run_dir: str, device="cuda"):
 
 
 def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False,
-             normals: bool = False, normal_dir=None, normal_frame=None, surface: bool = False) -> dict:
+             normals: bool = False, normal_dir=None, normal_frame=None, surface: bool = False, metrics_device=None) -> dict:
     """Rebuild the model of one training run from its config.json + newest checkpoint and evaluate
     it on the run's eval split.  ``depth_stats``: the results gain median_depth_mse / gt_depth_mse_median /
     gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views).  ``normals``: the
     results gain normal_angle_deg (against the run's own normal priors, or those of ``normal_dir`` / ``normal_frame`` if
     given) and the render dump normal/.  ``surface``: the run's surface is exported beside the results
     (touch_gs_amd.export.export_tsdf with its defaults -> ``<out_json stem>_surface/``) and, when the capture has ground truth
-    (``gt_depth/``), the results gain surface_chamfer / surface_precision / surface_recall / surface_fscore."""
+    (``gt_depth/``), the results gain surface_chamfer / surface_precision / surface_recall / surface_fscore;
+    ``metrics_device``: passed to export_tsdf (None = scipy on the host, a GPU device = the HIP k-NN)."""
     from .dataset import Scene
     from .train import evaluate, render_views
     model, cfg, ckpt = load_model(run_dir, device)
@@ -71,7 +72,7 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
             raise ValueError("--surface needs a run trained on a capture")
         from .export import export_tsdf
         info = export_tsdf(run_dir, os.path.splitext(os.path.abspath(out_json))[0] + "_surface", device=device,
-                           loaded=(model, dict(cfg, checkpoint=ckpt), scene))
+                           loaded=(model, dict(cfg, checkpoint=ckpt), scene), metrics_device=metrics_device)
         for k in ("chamfer", "precision", "recall", "fscore"):
             if "surface_metrics" in info:
                 results["surface_" + k] = info["surface_metrics"][k]
@@ -100,6 +101,9 @@ def main(argv=None):
     ap.add_argument("--surface", action="store_true",
                     help="also export the run's surface (python -m touch_gs_amd.export tsdf, defaults) next to the results "
                          "and, for a capture with gt_depth/, add surface_chamfer / _precision / _recall / _fscore")
+    ap.add_argument("--metrics-device", "--metrics_device", dest="metrics_device", default=None,
+                    help="--surface: find the metrics' nearest neighbours with the HIP k-NN on this device (e.g. cuda); "
+                         "default: scipy cKDTree on the host")
     a = ap.parse_args(argv)
     full_exp_dir = os.path.join(a.output_dir, a.exp_name)
     os.makedirs(full_exp_dir, exist_ok=True)
@@ -110,7 +114,7 @@ def main(argv=None):
             continue
         out_json = os.path.join(full_exp_dir, f"{a.exp_name}_{len(done) + 1}.json")
         res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders", depth_stats=a.depth_stats,
-                       normals=a.normals, surface=a.surface)
+                       normals=a.normals, surface=a.surface, metrics_device=a.metrics_device)
         print(out_json, json.dumps(res))
         done.append(out_json)
         if len(done) == a.past_n_trials:

@@ -31,8 +31,15 @@ from .optim import GaussianParams
 SH_C0 = 0.28209479177387814
 
 
+def knn_scale_hip(means_dev: torch.Tensor) -> torch.Tensor:
+    """[N] on the device: the mean distance to the 3 nearest neighbours from the exact HIP k-NN (ops.knn),
+    clamped like the torch path of ``init_params``: ``mean(sqrt(dist2[:, :3]), 1).clamp_min(1e-5)``."""
+    dist2, _ = ops.knn(means_dev, 3)
+    return dist2[:, :3].sqrt().mean(1).clamp_min(1e-5)
+
+
 def init_params(n: int, K: int, device, seed_points=None, extent: float = 1.0, seed: int = 0,
-                seed_fraction: float = 0.5) -> GaussianParams:
+                seed_fraction: float = 0.5, knn: str = "torch") -> GaussianParams:
     """``n`` initial Gaussians: the touch point cloud (points_touch.npy -- the object's touched surface,
     utils/create_point_cloud_from_touches.py:243-244) + a uniform random fill of the cube [-extent, extent]^3 for
     everything the fingers never reached (table, background), Splatfacto-style: scales from the mean distance to the
@@ -41,7 +48,12 @@ def init_params(n: int, K: int, device, seed_points=None, extent: float = 1.0, s
     A touch cloud can hold far more points than ``n`` (every touch-depth pixel of every training view): it is then
     SUBSAMPLED uniformly at random to ``seed_fraction * n`` points, so that all views contribute and the rest of the
     scene still gets its random fill.  (Rounds 1-4 kept the first ``n`` points in file order -- the first views'
-    touches only -- and dropped the fill whenever the cloud was larger than ``n``.)"""
+    touches only -- and dropped the fill whenever the cloud was larger than ``n``.)
+
+    ``knn``: how the neighbour distances are found -- "torch" (the default): blocked ``cdist`` + ``topk``, N^2 distances;
+    "hip": the spatially indexed exact k-NN kernels (``knn_scale_hip``), which need the device to be a GPU."""
+    if knn not in ("torch", "hip"):
+        raise ValueError(f"init_params: knn must be 'torch' or 'hip', got {knn!r}")
     g = torch.Generator().manual_seed(seed)
     pts, cols = [], []
     if seed_points is not None and len(seed_points[0]):
@@ -63,12 +75,14 @@ def init_params(n: int, K: int, device, seed_points=None, extent: float = 1.0, s
     # a subsampled estimate would give the object's points the fill's spacing)
     md = means.to(device)
     blk = max(64, min(4096, (1 << 28) // max(N, 1)))   # <= 1 GiB of distances per block whatever N is
-    kd = torch.empty(N, device=md.device)
-    for b in range(0, N, blk):
-        d = torch.cdist(md[b:b + blk], md)
-        kd[b:b + blk] = d.topk(4, largest=False).values[:, 1:].mean(1).clamp_min(1e-5)
-    knn = kd.cpu()
-    scale = knn
+    if knn == "hip":
+        kd = knn_scale_hip(md)
+    else:
+        kd = torch.empty(N, device=md.device)
+        for b in range(0, N, blk):
+            d = torch.cdist(md[b:b + blk], md)
+            kd[b:b + blk] = d.topk(4, largest=False).values[:, 1:].mean(1).clamp_min(1e-5)
+    scale = kd.cpu()
     sh = torch.zeros(N, K, 3)
     sh[:, 0] = (colors - 0.5) / SH_C0
     quats = torch.nn.functional.normalize(torch.randn(N, 4, generator=g), dim=1)
@@ -245,6 +259,10 @@ def main(argv=None, view_hook=None):
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="mcmc: weight of the mean opacity in the loss")
     ap.add_argument("--scale-reg", type=float, default=0.01, help="mcmc: weight of the mean scale in the loss")
     ap.add_argument("--mcmc-min-opacity", type=float, default=0.005, help="mcmc: a Gaussian at or below this opacity is dead")
+    ap.add_argument("--init-knn", type=str, default="torch", choices=("torch", "hip"),
+                    help="how the initial scales find each seed's 3 nearest neighbours: torch = blocked cdist + topk (N^2 "
+                         "distances); hip = the exact k-NN kernels (csrc/knn.hip).  Recorded in config.json; a config "
+                         "without the key was initialised with torch")
     args = ap.parse_args(argv)
 
     few = args.preset == "few-view"
@@ -276,7 +294,7 @@ def main(argv=None, view_hook=None):
             raise SystemExit("--mono-depth-mult > 0 needs --mono-depth-dir with at least one map")
         views, i_train, i_eval = scene.views, list(scene.i_train), list(scene.i_eval)
         params = init_params(args.num_gaussians, K, dev, scene.seed_points(), extent=args.random_extent, seed=args.seed,
-                             seed_fraction=args.seed_fraction)
+                             seed_fraction=args.seed_fraction, knn=args.init_knn)
         scene_name = os.path.basename(os.path.normpath(args.data))
     cfg = ModelConfig(sh_degree=args.sh_degree, depth_loss_mult=args.depth_loss_mult,
                       depth_loss_type=args.depth_loss_type, uncertainty_weight=args.uncertainty_weight,

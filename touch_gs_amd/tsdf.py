@@ -271,15 +271,34 @@ def fuse_model(model, cams, bounds, resolution: Optional[int] = 256, voxel_size:
     return vol
 
 
-def surface_metrics(points, gt_points, tau: float) -> dict:
+def nearest_distances_device(p, g, device):
+    """(d_pg [len(p)], d_gp [len(g)]) float64: the nearest-neighbour distances between two fp64 clouds from the exact HIP
+    k-NN (ops.knn, k = 1).  Both clouds lose their common fp64 centroid before the cast to fp32, so a capture
+    far from the origin keeps its digits; d2 is formed in fp32, the root and everything after it in fp64."""
+    import torch
+    from . import ops
+    c = np.concatenate([p, g]).mean(0)
+    tp = torch.from_numpy((p - c).astype(np.float32)).to(device)
+    tg = torch.from_numpy((g - c).astype(np.float32)).to(device)
+    d_pg = ops.knn(tg, 1, queries=tp)[0][:, 0].double().sqrt().cpu().numpy()
+    d_gp = ops.knn(tp, 1, queries=tg)[0][:, 0].double().sqrt().cpu().numpy()
+    return d_pg, d_gp
+
+
+def surface_metrics(points, gt_points, tau: float, device=None) -> dict:
     """chamfer = the mean of the two directed mean nearest-neighbour distances; precision = the share of ``points`` within
-    ``tau`` of ``gt_points``, recall = the share of ``gt_points`` within ``tau`` of ``points``, fscore = their harmonic mean."""
-    from scipy.spatial import cKDTree
+    ``tau`` of ``gt_points``, recall = the share of ``gt_points`` within ``tau`` of ``points``, fscore = their harmonic mean.
+    ``device`` None (the default): two scipy cKDTree queries in fp64 on the host; a GPU device: ``nearest_distances_device``
+    (fp32 squared distances of the centred clouds; the means and shares are formed in fp64 either way)."""
     p, g = np.asarray(points, dtype=np.float64).reshape(-1, 3), np.asarray(gt_points, dtype=np.float64).reshape(-1, 3)
     if len(p) == 0 or len(g) == 0:
         return dict(chamfer=float("nan"), precision=0.0, recall=0.0, fscore=0.0, n_points=len(p), n_gt=len(g), tau=float(tau))
-    d_pg = cKDTree(g).query(p)[0]
-    d_gp = cKDTree(p).query(g)[0]
+    if device is not None:
+        d_pg, d_gp = nearest_distances_device(p, g, device)
+    else:
+        from scipy.spatial import cKDTree
+        d_pg = cKDTree(g).query(p)[0]
+        d_gp = cKDTree(p).query(g)[0]
     precision, recall = float((d_pg <= tau).mean()), float((d_gp <= tau).mean())
     fscore = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
     return dict(chamfer=float(0.5 * (d_pg.mean() + d_gp.mean())), precision=precision, recall=recall, fscore=fscore,
