@@ -949,6 +949,48 @@ int tgs_knn_query(int n_q, const float* queries /*[n_q,3]*/, const int32_t* q_or
                   const float* sorted_pts, const float* boxes, int k, int exclude_self, float* dist2 /*[n_q,k]*/,
                   int32_t* idx /*[n_q,k]*/, void* stream);
 
+/* Per-view bilateral grid: spatially varying colour correction  C'[p] = A(p) C[p] + b(p)  (an ADDITION within TGS_VERSION
+ *     320: no struct and no earlier signature changes; csrc/bilagrid.hip).  The grid of one view is
+ *     g[GH][GW][L][12] float32 in DEVICE memory, the last axis a row-major 3x4 [A | b]; every dimension >= 2 (GW, GH <= 4096,
+ *     L <= 64); the identity everywhere = no change.  rgb [H,W,3] is tgs_rasterize_fwd's out_rgb; there is no clamp.
+ * COORDINATES of pixel (px, py) with colour C, every operation rounded to fp32 on its own, in this order:
+ *         gx = (float(px) + 0.5f) * sx,  sx = float(GW-1) / float(W);  gy likewise;
+ *         luma = (0.299f r + 0.587f g) + 0.114f b;  z = min(max(luma, 0), 1) * float(L-1);
+ *         ix = min(int(gx), GW-2), fx = gx - float(ix);  iy, fy and iz, fz likewise;  inside = luma > 0 && luma < 1.
+ * tgs_bilagrid_fwd: A(p) = the trilinear blend of the 8 corners in lerp form a + f (b - a): along x, then y (giving A0, A1 at
+ *     the levels iz, iz + 1), then z;  rgb_out[p][c] = ((A[c][0] r + A[c][1] g) + A[c][2] b) + A[c][3].  One launch.
+ * tgs_bilagrid_bwd: the RGB loss is taken on C' (recomputed here with the forward's bits, not read):
+ *         v'[p][c] = v_img[p][c] + l1_weight * sign(C'[p][c] - gt[p][c]),  sign(0) = 0;
+ *     gt NULL = no L1 term, v_img NULL = no upstream image, both NULL = zeros (the conventions of tgs_exposure_bwd).
+ *     v_rgb[p][k] = sum_c A[c][k] v'[p][c] + wl[k] (L-1) inside sum_c v'[p][c] ((A1 - A0) C1)[c],  C1 = (C, 1), wl the luma
+ *         weights: the upstream image tgs_rasterize_bwd takes, with TgsLossSpec.gt_rgb = NULL.
+ *     grad [2][n] or NULL, n = GH GW L 12: G[v][c][k] = sum_p w_v(p) v'[p][c] C1[p][k] (w_v the trilinear weight of vertex v,
+ *         zero outside the pixel's cell), then per entry the sum of the absolute values of those products (the masses).
+ *     out[TGS_BILAGRID_OUT]: [0] 1 = valid, 0 = the frame was void (guard[1] != 0: everything else is 0 too, `state` keeps
+ *         every bit; v_rgb is still written); [1] l1_weight * sum |C' - gt|; [2] W * H; [3] TV(g), unweighted; [4..7] 0.
+ *         TV(g) = sum over the axes x, y, z of (1 / n_axis) sum (g[next] - g[this])^2 over all 12 channels, n_axis the
+ *         number of differences along the axis (gsplat's total_variation_loss of one grid).
+ *     scratch[tgs_bilagrid_scratch_floats(...)]: tgs_bilagrid_num_partials(...) rows of tgs_bilagrid_row_floats(L) floats,
+ *         one per workgroup, then the staged gradient and the value partials; overwritten.
+ *     state[3 n + TGS_BILAGRID_TAIL] or NULL (gradient only): one view's optimizer row {[0,n) grid, [n,2n) exp_avg, [2n,3n)
+ *         exp_avg_sq, [3n] steps taken t, [3n+1] beta1^t, [3n+2] beta2^t (running products; 1 at t = 0), then zeros}.  On a
+ *         valid frame grad = G + tv_weight dTV/dg with dTV read from the grid BEFORE the step, t and the products advance,
+ *         and every entry takes one Adam step (the update of tgs_adam_step) with the bias corrections from the products.
+ *         grid may be state itself: the row is written by the last launch only.
+ *     Three launches, no float atomics: the shape of every sum depends on (W, H, GW, GH, L) alone, the same inputs give the
+ *     same bits.  No host synchronisation.  Every argument is checked before any launch (TGS_E_ARG). */
+#define TGS_BILAGRID_OUT  8    /* floats of the result */
+#define TGS_BILAGRID_TAIL 16   /* floats behind the 3 n entries of one view's state row */
+int tgs_bilagrid_num_partials(int W, int H, int GW, int GH, int L);      /* rows of the scratch; 0 = bad dimensions */
+size_t tgs_bilagrid_row_floats(int L);                                   /* floats of one such row: 4 L 24 + 8 */
+size_t tgs_bilagrid_scratch_floats(int W, int H, int GW, int GH, int L); /* floats of the whole scratch */
+int tgs_bilagrid_fwd(int W, int H, int GW, int GH, int L, const float* rgb, const float* grid, float* rgb_out, void* stream);
+int tgs_bilagrid_bwd(int W, int H, int GW, int GH, int L, const float* rgb, const float* grid,
+                     const float* gt /*may be NULL*/, float l1_weight, const float* v_img /*may be NULL*/, float tv_weight,
+                     float* v_rgb, float* scratch, float* grad /*[2][n], may be NULL*/, float* out /*[8]*/,
+                     const int32_t* guard /*may be NULL*/, float* state /*[3n+16] or NULL = gradient only*/,
+                     float lr, float beta1, float beta2, float eps, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Peer exchange: the data-parallel gradient exchange by direct stores into IPC-mapped peer memory (all 7 xGMI
  * links of a rank at once, no collective launch) -- the alternative to RCCL that touch_gs_amd.parallel selects

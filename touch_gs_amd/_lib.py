@@ -17,6 +17,9 @@ POSE_OUT = 32     # TGS_POSE_OUT
 EXPO_OUT = 32     # TGS_EXPO_OUT: floats of tgs_exposure_bwd's result and of a row of its scratch
 EXPO_STATE = 48   # TGS_EXPO_STATE: floats of one view's exposure row (E | exp_avg | exp_avg_sq | t, beta1^t, beta2^t | 0...)
 EXPO_CHUNK = 2048  # pixels per workgroup of k_expo_bwd_tiles (csrc/exposure.hip): tgs_exposure_num_partials = ceil(W H / it)
+BILAGRID_OUT = 8      # TGS_BILAGRID_OUT: floats of tgs_bilagrid_bwd's result
+BILAGRID_TAIL = 16    # TGS_BILAGRID_TAIL: floats behind the 3 n entries of one view's bilateral-grid row (t, beta1^t, beta2^t, 0...)
+BILAGRID_CHUNK = 1024  # pixels per workgroup of k_bg_cells (csrc/bilagrid.hip): a cell's pixel rectangle is cut into chunks of it
 BLOCK = 16
 KNN_MAX_K = 16    # TGS_KNN_MAX_K
 KNN_BOX = 256     # TGS_KNN_BOX: reference points per box of tgs_knn_build
@@ -151,6 +154,11 @@ SIGNATURES = {
     "tgs_exposure_num_partials": (C.c_int, [_I, _I]),
     "tgs_exposure_fwd": (C.c_int, [_I, _I, _P, _P, _P, _P]),
     "tgs_exposure_bwd": (C.c_int, [_I, _I, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [_P]),
+    "tgs_bilagrid_num_partials": (C.c_int, [_I] * 5),
+    "tgs_bilagrid_row_floats": (C.c_size_t, [_I]),
+    "tgs_bilagrid_scratch_floats": (C.c_size_t, [_I] * 5),
+    "tgs_bilagrid_fwd": (C.c_int, [_I] * 5 + [_P, _P, _P, _P]),
+    "tgs_bilagrid_bwd": (C.c_int, [_I] * 5 + [_P, _P, _P, C.c_float, _P, C.c_float, _P, _P, _P, _P, _P, _P] + [C.c_float] * 4 + [_P]),
     "tgs_gpis_render": (C.c_int, [_I, _P, _I, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.POINTER(TgsGpisView), _P, _P, _P, _P, _P]),
     "tgs_tsdf_integrate": (C.c_int, [_I, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, C.POINTER(TgsTsdfView), _P]),
     "tgs_tsdf_extract_count": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, C.c_float, _P, _P]),

@@ -6,7 +6,7 @@ OUT="$HERE/../lib"
 mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wall -Wno-unused-function $TGS_EXTRA_FLAGS"
-SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gpis tsdf peer mcmc knn"
+SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gpis tsdf peer mcmc knn bilagrid"
 # raster.hip: the SLP vectoriser pairs the per-pixel FMAs into v_pk_fma_f32, which on gfx950 costs
 # 1.84x a plain v_fma_f32 and needs register-pair shuffles (v_mov) around it: K7 127 -> 100 VGPRs and
 # -7 % time, K6 -3 % without it (measured, same box)
@@ -25,8 +25,11 @@ SRCS="api project binning raster optim imgloss depthcorr depthnormal exposure gp
 # mcmc.hip: -ffp-contract=off for the same reason (tests/mcmc_ref.py emulates the noise term); the Adam update inside it is
 # adam1's explicit fmaf chain whatever the flag, which keeps it bit-identical to K9.
 # knn.hip: -ffp-contract=off for the same reason (tests/knn_ref.py forms d2 in fp32 NumPy and the GPU test asks for equal bits).
+# bilagrid.hip: -ffp-contract=off for the same reason (tests/bilagrid_ref.py forms the cell coordinates in fp32 NumPy), and
+# because bg_axis / bg_guide / bg_slice are inlined into the forward and into the backward, which recomputes the cell and the
+# corrected image and must form the forward's bits, so that a pixel lands in the same cell and sign() decides alike.
 declare -A EXTRA=([raster]="-fno-slp-vectorize" [imgloss]="-fno-slp-vectorize" [project]="-ffp-contract=on"
-                  [depthnormal]="-ffp-contract=on" [exposure]="-ffp-contract=on" [tsdf]="-ffp-contract=off" [mcmc]="-ffp-contract=off" [knn]="-ffp-contract=off")
+                  [depthnormal]="-ffp-contract=on" [exposure]="-ffp-contract=on" [tsdf]="-ffp-contract=off" [mcmc]="-ffp-contract=off" [knn]="-ffp-contract=off" [bilagrid]="-ffp-contract=off")
 pids=()
 for s in $SRCS; do
   [ -f "$HERE/$s.hip" ] || continue

@@ -1287,6 +1287,134 @@ def apply_exposure(rgb, E):
 
 
 # ------------------------------------------------------------------------------------------------
+# per-view bilateral grid C' = A(p) C + b(p) (csrc/bilagrid.hip)
+# ------------------------------------------------------------------------------------------------
+def bilagrid_sizes(W: int, H: int, shape):
+    """-> (n, scratch floats) of a W x H frame under a grid of ``shape`` = (GW, GH, L): n = GH GW L 12 entries, and the
+    scratch :func:`bilagrid_bwd` needs (tgs_bilagrid_scratch_floats).  Functions of the five integers alone."""
+    GW, GH, L = (int(x) for x in shape)
+    s = _lib.load().tgs_bilagrid_scratch_floats(W, H, GW, GH, L)
+    if s == 0:
+        raise ValueError(f"bilagrid: bad sizes: image {W} x {H}, grid (GW, GH, L) = {(GW, GH, L)} "
+                         "(every grid dimension >= 2, GW and GH <= 4096, L <= 64)")
+    return GH * GW * L * 12, int(s)
+
+
+def _bila_grid(grid, shape, what: str):
+    """The n = GH GW L 12 floats a kernel reads: a [GH,GW,L,12] / [n] tensor, or the head of a view's [3n+16] state row."""
+    GW, GH, L = (int(x) for x in shape)
+    n = GH * GW * L * 12
+    if (not torch.is_tensor(grid) or not grid.is_cuda or grid.dtype != torch.float32 or not grid.is_contiguous()
+            or grid.numel() < n):
+        raise ValueError(f"{what}: grid must be a contiguous float32 device tensor of at least GH GW L 12 = {n} elements")
+    return grid
+
+
+def _bila_buf(t, n: int, what: str, dev, dtype=torch.float32, exact: bool = False):
+    if (not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or not t.is_contiguous()
+            or (t.numel() != n if exact else t.numel() < n)):
+        raise ValueError(f"bilagrid_bwd: {what} must be a contiguous {dtype} tensor on {dev} of "
+                         f"{'' if exact else 'at least '}{n} elements")
+    return t
+
+
+def bilagrid_fwd(rgb, grid, shape, out=None):
+    """-> C' [H,W,3]: ``rgb`` through the bilateral grid ``grid`` ([GH,GW,L,12], the last axis a row-major 3x4 [A | b]; or a
+    view's state row) of ``shape`` = (GW, GH, L), sliced trilinearly at the pixel's position and the luminance of its
+    colour.  No clamp.  No host sync.  (tgs_bilagrid_fwd)"""
+    lib = _lib.load()
+    rgb = _f32c(rgb.detach())
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"bilagrid_fwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    H, W = rgb.shape[0], rgb.shape[1]
+    GW, GH, L = (int(x) for x in shape)
+    bilagrid_sizes(W, H, shape)
+    if out is None:
+        out = torch.empty_like(rgb)
+    elif out.device != rgb.device or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != rgb.shape:
+        raise ValueError("bilagrid_fwd: out must be a contiguous float32 tensor of rgb's shape on rgb's device")
+    check(lib.tgs_bilagrid_fwd(W, H, GW, GH, L, ptr(rgb), ptr(_bila_grid(grid, shape, "bilagrid_fwd")), ptr(out), _stream()),
+          "tgs_bilagrid_fwd")
+    return out
+
+
+def bilagrid_bwd(rgb, grid, shape, gt=None, l1_weight: float = 0.0, v_img=None, tv_weight: float = 0.0, guard=None,
+                 state=None, adam=None, want_grad: bool = True, out=None):
+    """The backward of :func:`bilagrid_fwd` with the L1 term taken on C' -> (out8, v_rgb, grad).  (tgs_bilagrid_bwd)
+
+    ``v' = v_img + l1_weight * sign(C' - gt)`` (either image may be None); ``v_rgb`` (the guide's gradient included) is the
+    upstream image :func:`rasterize_bwd` takes (with a loss spec WITHOUT ``gt_rgb``); ``grad`` [2, n] = dL/dgrid of the data
+    term, then its masses (None with ``want_grad=False``, which needs ``state``); ``out8`` = valid flag |
+    ``l1_weight * sum |C' - gt|`` | pixel count | TV(grid), unweighted | zeros.  ``guard`` = the frame's status word: an
+    overflowed frame gives a zero ``out8`` and leaves ``state`` alone.  ``state`` = a view's [3n+16] row
+    (:class:`touch_gs_amd.bilagrid.BilagridSet`), stepped in the same call on ``G + tv_weight dTV`` with
+    ``adam = dict(lr, betas, eps)``; None = gradient only.  ``grid`` may be ``state``.
+    ``out`` = (result [8], scratch [>= bilagrid_sizes(W, H, shape)[1]]) to allocate nothing but ``v_rgb`` and ``grad``;
+    (result, scratch, v_rgb [H,W,3]) or (result, scratch, v_rgb, grad [2, n]) to allocate nothing.  No host sync."""
+    lib = _lib.load()
+    rgb, gt, v_img = _f32c(rgb.detach()), _f32c(gt), _f32c(v_img)
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"bilagrid_bwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    for name, t in (("gt", gt), ("v_img", v_img)):
+        if t is not None and t.shape != rgb.shape:
+            raise ValueError(f"bilagrid_bwd: {name} {tuple(t.shape)} does not match rgb {tuple(rgb.shape)}")
+    H, W = rgb.shape[0], rgb.shape[1]
+    GW, GH, L = (int(x) for x in shape)
+    dev = rgb.device
+    n, S = bilagrid_sizes(W, H, shape)
+    if out is None:
+        out = (torch.empty(_lib.BILAGRID_OUT, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev))
+    res, scratch = out[0], out[1]
+    _bila_buf(res, _lib.BILAGRID_OUT, "out[0] (the result)", dev, exact=True)
+    _bila_buf(scratch, S, "out[1] (the scratch, tgs_bilagrid_scratch_floats floats)", dev)
+    if guard is not None:
+        _bila_buf(guard, 2, "guard (the frame's status word)", dev, dtype=torch.int32)
+    lr = b1 = b2 = eps = 0.0
+    if state is not None:
+        if adam is None:
+            raise ValueError("bilagrid_bwd: a state row needs adam = dict(lr, betas, eps)")
+        _bila_buf(state, 3 * n + _lib.BILAGRID_TAIL, "state (a view's row)", dev, exact=True)
+        lr, (b1, b2), eps = adam["lr"], adam.get("betas", (0.9, 0.999)), adam.get("eps", 1e-15)
+    elif not want_grad:
+        raise ValueError("bilagrid_bwd: want_grad=False needs a state row to step")
+    grad = None
+    if want_grad:
+        grad = _bila_buf(out[3], 2 * n, "out[3] (grad, [2, n])", dev, exact=True) if len(out) > 3 else \
+            torch.empty(2, n, dtype=torch.float32, device=dev)
+    v_rgb = _bila_buf(out[2], rgb.numel(), "out[2] (v_rgb)", dev, exact=True) if len(out) > 2 else torch.empty_like(rgb)
+    check(lib.tgs_bilagrid_bwd(W, H, GW, GH, L, ptr(rgb), ptr(_bila_grid(grid, shape, "bilagrid_bwd")), ptr(gt),
+                               C.c_float(l1_weight), ptr(v_img), C.c_float(tv_weight), ptr(v_rgb), ptr(scratch), ptr(grad),
+                               ptr(res), ptr(guard), ptr(state), C.c_float(lr), C.c_float(b1), C.c_float(b2), C.c_float(eps),
+                               _stream()), "tgs_bilagrid_bwd")
+    return res, v_rgb, grad
+
+
+class _ApplyBilagrid(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgb, grid):
+        gd = _f32c(grid.detach())
+        ctx.save_for_backward(rgb.detach(), gd)
+        GH, GW, L = gd.shape[:3]
+        return bilagrid_fwd(rgb, gd, (GW, GH, L))
+
+    @staticmethod
+    def backward(ctx, g):
+        rgb, gd = ctx.saved_tensors
+        GH, GW, L = gd.shape[:3]
+        _, v_rgb, grad = bilagrid_bwd(rgb, gd, (GW, GH, L), gt=None, l1_weight=0.0, v_img=g)
+        return v_rgb, grad[0].view(gd.shape)
+
+
+def apply_bilagrid(rgb, grid):
+    """C' = A(p) rgb + b(p) for a bilateral grid ``grid`` [GH,GW,L,12] on the device, differentiable in ``rgb`` (the guide's
+    gradient included) and in ``grid`` (the two kernels of :func:`bilagrid_fwd` / :func:`bilagrid_bwd`): what the
+    gsplat-shaped and INRIA-shaped surfaces compose with their own losses.  No host sync."""
+    if grid.dim() != 4 or grid.shape[3] != 12:
+        raise ValueError(f"apply_bilagrid: grid must be [GH,GW,L,12], got {tuple(grid.shape)}")
+    return _ApplyBilagrid.apply(rgb, grid)
+
+
+# ------------------------------------------------------------------------------------------------
 # fixed-budget MCMC strategy (csrc/mcmc.hip, touch_gs_amd/mcmc.py)
 # ------------------------------------------------------------------------------------------------
 def mcmc_spec(opacity_reg: float = 0.01, scale_reg: float = 0.01, noise_lr: float = 5e5, gate_k: float = 100.0,

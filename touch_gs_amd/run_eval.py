@@ -40,7 +40,8 @@ def load_model(run_dir: str, device="cuda"):
 
 
 def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_stats: bool = False,
-             normals: bool = False, normal_dir=None, normal_frame=None, surface: bool = False, metrics_device=None) -> dict:
+             normals: bool = False, normal_dir=None, normal_frame=None, surface: bool = False, metrics_device=None,
+             color_correct: bool = False) -> dict:
     """Rebuild the model of one training run from its config.json + newest checkpoint and evaluate
     it on the run's eval split.  ``depth_stats``: the results gain median_depth_mse / gt_depth_mse_median /
     gt_object_depth_mse_median and the render dump median_depth/ and uncertainty/ (train.render_views).  ``normals``: the
@@ -48,7 +49,9 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
     given) and the render dump normal/.  ``surface``: the run's surface is exported beside the results
     (touch_gs_amd.export.export_tsdf with its defaults -> ``<out_json stem>_surface/``) and, when the capture has ground truth
     (``gt_depth/``), the results gain surface_chamfer / surface_precision / surface_recall / surface_fscore;
-    ``metrics_device``: passed to export_tsdf (None = scipy on the host, a GPU device = the HIP k-NN)."""
+    ``metrics_device``: passed to export_tsdf (None = scipy on the host, a GPU device = the HIP k-NN).  ``color_correct``:
+    the results gain cc_psnr / cc_ssim (train.evaluate: each render fitted to its ground truth by a least-squares 3x4 affine
+    colour transform before the metric); no other key changes."""
     from .dataset import Scene
     from .train import evaluate, render_views
     model, cfg, ckpt = load_model(run_dir, device)
@@ -65,7 +68,7 @@ def eval_run(run_dir: str, out_json: str, render_dir=None, device="cuda", depth_
         apply_refined_poses(run_dir, scene.views, scene.names)   # training views as the run left them (held-out ones are not listed)
         idx = list(scene.i_eval) or list(scene.i_train)[:1]
         views, names, scale = [scene.views[i] for i in idx], [scene.names[i] for i in idx], scene.scale
-    results = evaluate(model, views, depth_stats=depth_stats, normals=normals)
+    results = evaluate(model, views, depth_stats=depth_stats, normals=normals, color_correct=color_correct)
     results.setdefault("lpips", float("nan"))   # get_results.py:38 indexes it unconditionally
     if surface:
         if cfg.get("synthetic"):
@@ -104,6 +107,10 @@ def main(argv=None):
     ap.add_argument("--metrics-device", "--metrics_device", dest="metrics_device", default=None,
                     help="--surface: find the metrics' nearest neighbours with the HIP k-NN on this device (e.g. cuda); "
                          "default: scipy cKDTree on the host")
+    ap.add_argument("--color-correct", "--color_correct", dest="color_correct", action="store_true",
+                    help="also report cc_psnr / cc_ssim: each render is fitted to its ground truth by a least-squares 3x4 affine "
+                         "colour transform before the metric (the evaluation of runs with per-view colour models: --exposure-lr, "
+                         "--bilagrid-lr); the other keys do not change")
     a = ap.parse_args(argv)
     full_exp_dir = os.path.join(a.output_dir, a.exp_name)
     os.makedirs(full_exp_dir, exist_ok=True)
@@ -114,7 +121,8 @@ def main(argv=None):
             continue
         out_json = os.path.join(full_exp_dir, f"{a.exp_name}_{len(done) + 1}.json")
         res = eval_run(run_dir, out_json, None if a.no_render else f"{a.exp_name}_renders", depth_stats=a.depth_stats,
-                       normals=a.normals, surface=a.surface, metrics_device=a.metrics_device)
+                       normals=a.normals, surface=a.surface, metrics_device=a.metrics_device,
+                       color_correct=a.color_correct)
         print(out_json, json.dumps(res))
         done.append(out_json)
         if len(done) == a.past_n_trials:

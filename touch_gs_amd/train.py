@@ -92,16 +92,32 @@ def init_params(n: int, K: int, device, seed_points=None, extent: float = 1.0, s
 
 
 @torch.no_grad()
-def evaluate(model: DepthGaussianSplattingModel, views, depth_stats: bool = False, normals: bool = False) -> dict:
+def color_corrected(rgb: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+    """``rgb`` [H,W,3] through the 3x4 affine colour transform that fits it to ``gt`` in the least-squares sense (the normal
+    equations in fp64; a rank-deficient fit, e.g. a constant render, takes the minimum-norm solution): the common gauge of
+    evaluation under per-view colour models (gsplat's evaluation under bilateral grids).  No clamp."""
+    X = torch.cat([rgb.reshape(-1, 3).double(), torch.ones(rgb.shape[0] * rgb.shape[1], 1, dtype=torch.float64, device=rgb.device)], dim=1)
+    M = torch.linalg.pinv((X.T @ X).cpu(), hermitian=True).to(rgb.device) @ (X.T @ gt.reshape(-1, 3).double())
+    return (X @ M).reshape(rgb.shape).float().contiguous()
+
+
+def evaluate(model: DepthGaussianSplattingModel, views, depth_stats: bool = False, normals: bool = False,
+             color_correct: bool = False) -> dict:
     """Mean of the eval metrics over ``views``.  ``depth_stats``: also median_depth_mse / gt_depth_mse_median /
     gt_object_depth_mse_median (the median depth under the masks of the expected-depth keys, whose values do not change).
-    ``normals``: also normal_angle_deg over the views that carry a normal prior."""
+    ``normals``: also normal_angle_deg over the views that carry a normal prior.  ``color_correct``: also cc_psnr / cc_ssim,
+    psnr and ssim of each render after ``color_corrected`` against its ground truth; no other key changes."""
     acc = {}
     kw = dict(normals=True) if normals else {}
     for v in views:
         out = (model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), depth_stats=True, **kw) if depth_stats else
                model.get_outputs(v.cam, sh_degree=model.active_sh_degree(), **kw))
         m, _ = model.get_image_metrics_and_images(out, v)
+        if color_correct:
+            cc = color_corrected(out["rgb"].detach(), v.rgb)
+            H, W = v.rgb.shape[:2]
+            m["cc_psnr"] = float(-10.0 * torch.log10(((cc - v.rgb) ** 2).mean()))
+            m["cc_ssim"] = float(ops.ssim_fwd_bwd(cc, v.rgb, want_grad=False)[0]) / (3 * H * W)
         for k, x in m.items():
             acc.setdefault(k, []).append(x)
     return {k: float(sum(x) / len(x)) for k, x in acc.items()}
@@ -250,6 +266,15 @@ def main(argv=None, view_hook=None):
                          "colour transform (INRIA's exposure_lr is 0.01); 0 = off (the default under both presets)")
     ap.add_argument("--exposure-l2", type=float, default=0.0, help="pull of the exposure matrices towards the identity")
     ap.add_argument("--exposure-start-step", type=int, default=0, help="first step that compensates and learns exposures")
+    ap.add_argument("--bilagrid-lr", type=float, default=0.0,
+                    help="per-view bilateral grids of the TRAINING views (spatially varying colour correction, gsplat's "
+                         "use_bilateral_grid): peak Adam learning rate of each view's grid of 3x4 affine colour transforms "
+                         "(gsplat's is 2e-3; warm-up from 1 %% over 1000 steps, decay to 1 %% at the last step); 0 = off (the "
+                         "default under both presets).  Does not combine with --exposure-lr")
+    ap.add_argument("--bilagrid-shape", type=int, nargs=3, default=(16, 16, 8), metavar=("GW", "GH", "L"),
+                    help="vertices of a grid along x, y and the luminance axis")
+    ap.add_argument("--bilagrid-tv", type=float, default=10.0, help="weight of the grids' total variation")
+    ap.add_argument("--bilagrid-start-step", type=int, default=0, help="first step that corrects and learns the grids")
     ap.add_argument("--strategy", type=str, default="default", choices=("default", "mcmc"),
                     help="refinement strategy: default = Splatfacto's clone / split / cull (--densify); mcmc = fixed-budget "
                          "3DGS-MCMC (touch_gs_amd/mcmc.py): relocation of dead Gaussians, growth by 5 %% up to --cap-max, opacity "
@@ -306,6 +331,8 @@ def main(argv=None, view_hook=None):
                       normal_max_jump=args.normal_max_jump, pose_lr_rot=args.pose_lr_rot, pose_lr_trans=args.pose_lr_trans,
                       pose_l2_rot=args.pose_l2_rot, pose_l2_trans=args.pose_l2_trans, pose_start_step=args.pose_start_step,
                       exposure_lr=args.exposure_lr, exposure_l2=args.exposure_l2, exposure_start_step=args.exposure_start_step,
+                      bilagrid_lr=args.bilagrid_lr, bilagrid_shape=tuple(args.bilagrid_shape), bilagrid_tv=args.bilagrid_tv,
+                      bilagrid_start_step=args.bilagrid_start_step,
                       opacity_reg=args.opacity_reg if use_mcmc else 0.0, scale_reg=args.scale_reg if use_mcmc else 0.0,
                       mcmc_noise_lr=args.mcmc_noise_lr if use_mcmc else 0.0)
     model = DepthGaussianSplattingModel(cfg, params)
@@ -315,12 +342,16 @@ def main(argv=None, view_hook=None):
         raise ValueError("--pose-lr-rot / --pose-lr-trans: pose refinement is not supported in data-parallel runs")
     if cfg.exposure_lr > 0 and dp.active:
         raise ValueError("--exposure-lr: exposure compensation is not supported in data-parallel runs")
+    if cfg.bilagrid_lr > 0 and dp.active:
+        raise ValueError("--bilagrid-lr: bilateral grids are not supported in data-parallel runs")
     if use_mcmc and dp.active:
         raise ValueError("--strategy mcmc: the MCMC strategy is not supported in data-parallel runs")
     if view_hook is not None:
         view_hook(train_views, 1.0 if args.synthetic else scene.scale)
     model.enable_pose_refinement(train_views)     # held-out views are never refined; before a checkpoint is loaded
     model.enable_exposure(train_views)            # likewise: held-out views have no row and are rendered uncompensated
+    if model.enable_bilagrid(train_views) is not None:    # likewise: held-out views have no grid and are rendered uncorrected
+        model.bilagrid_set.max_steps = max(args.max_num_iterations, 1)    # the schedule decays to 1 % at the run's last step
     if cfg.spatial_sort:
         model.spatial_sort()
     if use_mcmc:
@@ -398,6 +429,9 @@ def main(argv=None, view_hook=None):
             if model.exposure_set is not None:
                 from .exposure import save_exposures
                 save_exposures(run_dir, model.exposure_set, train_names)
+            if model.bilagrid_set is not None:
+                from .bilagrid import save_bilagrids
+                save_bilagrids(run_dir, model.bilagrid_set, train_names)
     model.flush()
     if dp.world > 1:
         dp.assert_replicas_identical(model.params.flat)
