@@ -6,6 +6,7 @@ the scene of the data-parallel worker of tests/test_gpu_api_surfaces.py (4001 Ga
 views, seeds 7 / 99).  One line per mode:
 
     mode  step  optimizer.t  params.N  sha256(params.flat) sha256(exp_avg) sha256(exp_avg_sq)  C entry points of the last two steps
+    [color_set=sha256(state of the exposure / bilateral-grid set)]
 
 The entry points are recorded by wrapping the callables of the object ``_lib.load()`` returns (runs of one name as
 ``name*k``).  ``--dump DIR`` also saves the three buffers of every mode (to compare by largest difference if a mode is not
@@ -57,6 +58,9 @@ MODES = {
     "pose_exposure": (dict(pose_lr_rot=1e-3, pose_lr_trans=1e-3, exposure_lr=1e-2),
                       lambda m, v: (m.enable_pose_refinement(v), m.enable_exposure(v)), True, None),
     "mono_local_normal": (dict(mono_depth_local_mult=0.1, normal_prior_mult=0.1), None, True, priors),
+    "bilagrid": (dict(bilagrid_lr=2e-3, bilagrid_shape=(5, 3, 4)), lambda m, v: m.enable_bilagrid(v), True, None),
+    "exposure_c2f": (dict(exposure_lr=1e-2, num_downscales=1, resolution_schedule=4), lambda m, v: m.enable_exposure(v),
+                     False, None),
 }
 sha = lambda t: hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
 for mode in args.modes or MODES:
@@ -85,6 +89,7 @@ for mode in args.modes or MODES:
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
         torch.save([b.cpu() for b in bufs], os.path.join(args.dump, mode + ".pt"))
+    color_set = m.exposure_set or m.bilagrid_set    # the per-view colour correction's rows, where the mode has one
     print(mode, m.step, m.optimizer.t, m.params.N, *[sha(b) for b in bufs],
           " ".join(n if k == 1 else f"{n}*{k}" for n, k in runs), f"replays={getattr(m, 'speculative_replays', 0)}",
-          flush=True)
+          *([] if color_set is None else [f"color_set={sha(color_set.state)}"]), flush=True)

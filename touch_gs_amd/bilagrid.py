@@ -20,7 +20,8 @@ from typing import Dict, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
+from .colorcorr import ViewColorSet
 
 BILAGRIDS_FILE = "bilagrids.npz"
 DEFAULT_SHAPE = (16, 16, 8)     # (GW, GH, L)
@@ -44,27 +45,29 @@ def from_gsplat(grid: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.transpose(grid, (2, 3, 1, 0)))
 
 
-class BilagridSet:
-    """The grid rows of ``views`` (the FULL-resolution training views, recognised by identity; a downscaled form of a view
-    uses its parent's row: the caller asks with the parent)."""
+def _tv(g, axes):
+    """Total variation of a grid along ``axes``: the sum of the mean squared differences of neighbouring vertices."""
+    return sum(((g.narrow(a, 1, g.shape[a] - 1) - g.narrow(a, 0, g.shape[a] - 1)) ** 2).mean() for a in axes)
+
+
+class BilagridSet(ViewColorSet):
+    """The grid rows of ``views``, the full-resolution training views (``ViewColorSet``)."""
+    name, what, rate_field, start_field, l1_index = "bilagrid", "bilateral grids", "bilagrid_lr", "bilagrid_start_step", 1
 
     def __init__(self, views: Sequence, device, lr: float = 2e-3, shape=DEFAULT_SHAPE, tv_weight: float = 10.0,
                  betas=(0.9, 0.999), eps: float = 1e-15, warmup_steps: int = 1000, max_steps: int = 30000):
-        self.views = list(views)
         self.shape = tuple(int(x) for x in shape)
         if len(self.shape) != 3 or min(self.shape) < 2:
             raise ValueError(f"bilagrid_shape must be (GW, GH, L) with every dimension >= 2, got {tuple(shape)}")
         GW, GH, L = self.shape
-        self.n = GH * GW * L * 12
+        self.n, self.leaf_shape = GH * GW * L * 12, (GH, GW, L, 12)
         self.lr, self.tv_weight = float(lr), float(tv_weight)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.warmup_steps, self.max_steps = int(warmup_steps), max(int(max_steps), 1)
-        self._index: Dict[int, int] = {id(v): i for i, v in enumerate(self.views)}
         row = torch.zeros(3 * self.n + _lib.BILAGRID_TAIL, dtype=torch.float32)
         row[:self.n] = torch.from_numpy(identity_grid(self.shape).reshape(-1))
         row[3 * self.n + 1] = row[3 * self.n + 2] = 1.0      # beta^0
-        self.state = row.repeat(max(len(self.views), 1), 1)[:len(self.views)].contiguous().to(device)
-        self._scratch = None
+        super().__init__(views, device, row)
 
     def lr_at(self, step: int) -> float:
         """gsplat's schedule of the grids' rate, formed on the host from the step number: linear warm-up from 1 % over
@@ -77,41 +80,56 @@ class BilagridSet:
         """The optimizer constants of ``step`` in the form ``ops.bilagrid_bwd`` takes."""
         return dict(lr=self.lr_at(step), betas=self.betas, eps=self.eps)
 
-    def owns(self, view) -> bool:
-        i = self._index.get(id(view))
-        return i is not None and self.views[i] is view
-
-    def row(self, view) -> torch.Tensor:
-        """The view's [3n+16] row: a view INTO the state tensor (the kernels read the grid from its head and step it in place)."""
-        return self.state[self._index[id(view)]]
-
     def scratch(self, W: int, H: int) -> torch.Tensor:
         """The reduction scratch of ``ops.bilagrid_bwd`` for a W x H frame, kept between steps."""
-        GW, GH, L = self.shape
-        S = int(_lib.load().tgs_bilagrid_scratch_floats(W, H, GW, GH, L))
-        if self._scratch is None or self._scratch.numel() < S or self._scratch.device != self.state.device:
-            self._scratch = torch.empty(max(S, 1), dtype=torch.float32, device=self.state.device)
-        return self._scratch
+        return self._scratch_of(int(_lib.load().tgs_bilagrid_scratch_floats(W, H, *self.shape)))
+
+    def forward(self, rgb, row):
+        return ops.bilagrid_fwd(rgb, row, self.shape)
+
+    def backward_step(self, rgb, row, gt, l1_weight, v_img, guard, step, W, H):
+        return ops.bilagrid_bwd(rgb, row, self.shape, gt=gt, l1_weight=l1_weight, v_img=v_img, tv_weight=self.tv_weight,
+                                guard=guard, state=row, adam=self.adam(step), want_grad=False,
+                                out=(torch.empty(_lib.BILAGRID_OUT, dtype=torch.float32, device=rgb.device),
+                                     self.scratch(W, H)))[:2]
+
+    @classmethod
+    def loss_terms(cls, result, config) -> dict:
+        return {"bilagrid_tv_loss": config.bilagrid_tv * result[3]}
+
+    def apply(self, rgb, leaf):
+        return ops.apply_bilagrid(rgb, leaf)
+
+    def leaf_loss_terms(self, leaf) -> dict:
+        return {"bilagrid_tv_loss": self.tv_weight * _tv(leaf, (0, 1, 2))}
+
+    def metrics(self) -> dict:
+        if not self.views:
+            return {}
+        g = self.state[:, :self.n].view(-1, *self.leaf_shape)
+        return dict(bilagrid_tv=_tv(g, (1, 2, 3)),
+                    bilagrid_delta=(g - g.new_tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])).abs().mean())
 
     def grids(self) -> np.ndarray:
         """[n_views, GH, GW, L, 12] on the host, in the order of ``views`` (one copy; synchronises)."""
-        GW, GH, L = self.shape
-        return self.state[:, :self.n].detach().cpu().numpy().reshape(-1, GH, GW, L, 12)
+        return self.state[:, :self.n].detach().cpu().numpy().reshape(-1, *self.leaf_shape)
 
     def grid(self, view) -> np.ndarray:
         """The view's grid on the host, [GH, GW, L, 12].  Synchronises: for saving and reporting, not for the step."""
-        GW, GH, L = self.shape
-        return self.row(view)[:self.n].detach().cpu().numpy().reshape(GH, GW, L, 12)
+        return self.row(view)[:self.n].detach().cpu().numpy().reshape(self.leaf_shape)
 
     def state_dict(self) -> dict:
-        return dict(state=self.state.detach().cpu().clone(), shape=self.shape)
+        return dict(super().state_dict(), shape=self.shape)
 
     def load_state_dict(self, sd: dict) -> None:
         s = sd["state"]
         if tuple(sd.get("shape", self.shape)) != self.shape or tuple(s.shape) != tuple(self.state.shape):
             raise ValueError(f"checkpoint holds bilateral-grid rows of shape {tuple(s.shape)} for a grid "
                              f"{tuple(sd.get('shape', ()))}, the set {tuple(self.state.shape)} for {self.shape}")
-        self.state.copy_(s.to(torch.float32))
+        super().load_state_dict(sd)
+
+    def save(self, run_dir: str, names: Sequence[str]) -> str:
+        return save_bilagrids(run_dir, self, names)
 
 
 def save_bilagrids(run_dir: str, bs: BilagridSet, names: Sequence[str]) -> str:

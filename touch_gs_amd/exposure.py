@@ -13,49 +13,53 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Dict, Sequence
+from typing import Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
+from .colorcorr import ViewColorSet
 
 EXPOSURES_FILE = "exposures.json"
 
 
-class ExposureSet:
-    """The exposure rows of ``views`` (the FULL-resolution training views, recognised by identity; a downscaled form of a
-    view uses its parent's row: the caller asks with the parent)."""
+class ExposureSet(ViewColorSet):
+    """The exposure rows of ``views``, the full-resolution training views (``ViewColorSet``)."""
+    name, what, rate_field, start_field = "exposure", "exposure compensation", "exposure_lr", "exposure_start_step"
+    l1_index, n, leaf_shape = 25, 12, (3, 4)
 
     def __init__(self, views: Sequence, device, lr: float, betas=(0.9, 0.999), eps: float = 1e-15, l2: float = 0.0):
-        self.views = list(views)
         self.lr, self.betas, self.eps, self.l2 = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(l2)
-        self._index: Dict[int, int] = {id(v): i for i, v in enumerate(self.views)}
         row = torch.zeros(_lib.EXPO_STATE, dtype=torch.float32)
         row[0] = row[5] = row[10] = 1.0      # E = identity
         row[37] = row[38] = 1.0              # beta^0
-        self.state = row.repeat(max(len(self.views), 1), 1)[:len(self.views)].contiguous().to(device)
-        self._scratch = None
+        super().__init__(views, device, row)
 
     @property
     def adam(self) -> dict:
         """The optimizer constants in the form ``ops.exposure_bwd`` takes."""
         return dict(lr=self.lr, betas=self.betas, eps=self.eps, l2=self.l2)
 
-    def owns(self, view) -> bool:
-        i = self._index.get(id(view))
-        return i is not None and self.views[i] is view
-
-    def row(self, view) -> torch.Tensor:
-        """The view's [48] row: a view INTO the state tensor (the kernels read E from its head and step it in place)."""
-        return self.state[self._index[id(view)]]
-
     def scratch(self, W: int, H: int) -> torch.Tensor:
         """The reduction scratch of ``ops.exposure_bwd`` for a W x H frame, kept between steps."""
-        P = _lib.load().tgs_exposure_num_partials(W, H)
-        if self._scratch is None or self._scratch.shape[0] < P or self._scratch.device != self.state.device:
-            self._scratch = torch.empty(max(P, 1), _lib.EXPO_OUT, dtype=torch.float32, device=self.state.device)
-        return self._scratch
+        return self._scratch_of(_lib.load().tgs_exposure_num_partials(W, H), _lib.EXPO_OUT)
+
+    def forward(self, rgb, row):
+        return ops.exposure_fwd(rgb, row)
+
+    def backward_step(self, rgb, row, gt, l1_weight, v_img, guard, step, W, H):
+        return ops.exposure_bwd(rgb, row, gt=gt, l1_weight=l1_weight, v_img=v_img, guard=guard, state=row, adam=self.adam,
+                                out=(torch.empty(_lib.EXPO_OUT, dtype=torch.float32, device=rgb.device), self.scratch(W, H)))
+
+    def apply(self, rgb, leaf):
+        return ops.apply_exposure(rgb, leaf)
+
+    def metrics(self) -> dict:
+        if not self.views:
+            return {}
+        E = self.state[:, :12]
+        return dict(exposure_gain=E[:, [0, 5, 10]].mean(), exposure_offset=E[:, [3, 7, 11]].mean())
 
     def matrix(self, view) -> np.ndarray:
         """E of the view on the host, [3,4] float32.  Synchronises: for saving and reporting, not for the step."""
@@ -65,14 +69,8 @@ class ExposureSet:
         """[n_views, 3, 4] on the host, in the order of ``views`` (one copy; synchronises)."""
         return self.state[:, :12].detach().cpu().numpy().reshape(-1, 3, 4)
 
-    def state_dict(self) -> dict:
-        return dict(state=self.state.detach().cpu().clone())
-
-    def load_state_dict(self, sd: dict) -> None:
-        s = sd["state"]
-        if tuple(s.shape) != tuple(self.state.shape):
-            raise ValueError(f"checkpoint holds exposure rows of shape {tuple(s.shape)}, the set {tuple(self.state.shape)}")
-        self.state.copy_(s.to(torch.float32))
+    def save(self, run_dir: str, names: Sequence[str]) -> str:
+        return save_exposures(run_dir, self, names)
 
 
 def save_exposures(run_dir: str, es: ExposureSet, names: Sequence[str]) -> str:

@@ -25,10 +25,14 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ops
+from .bilagrid import BilagridSet
 from .camera import Camera
+from .exposure import ExposureSet
 from .optim import FusedAdam, GaussianParams
 
 DEPTH_LOSS_TYPES = ("DEPTH_UNCERTAINTY_WEIGHTED_LOSS", "SIMPLE_LOSS")
+# the per-view colour corrections (colorcorr.ViewColorSet): at most one is active, in ``model.color_set``
+COLOR_SETS = (ExposureSet, BilagridSet)
 
 
 @dataclasses.dataclass
@@ -250,8 +254,7 @@ class DepthGaussianSplattingModel:
         self._tuned_cams = {}
         self.pose_refiner = None    # enable_pose_refinement(views)
         self._pose_scratch = None
-        self.exposure_set = None    # enable_exposure(views)
-        self.bilagrid_set = None    # enable_bilagrid(views)
+        self.color_set = None       # enable_exposure(views) / enable_bilagrid(views): the one active ViewColorSet
         # every other field the train step keeps between calls is declared HERE: no method creates an attribute
         self.density = None         # enable_densification(): the DensityController | enable_mcmc(): the MCMCController
         self.mcmc = self._mcmc_gen = None   # enable_mcmc(): the TgsMcmcSpec of the step's kernel | the device generator of its noise
@@ -271,38 +274,35 @@ class DepthGaussianSplattingModel:
     def enable_exposure(self, views):
         """Learn an exposure matrix for each of ``views`` (the full-resolution TRAINING views; held-out views are not
         given and are rendered uncompensated) with the rate of the config; -> the ExposureSet, or None when the rate is 0."""
-        c = self.config
-        if c.exposure_lr <= 0:
-            self.exposure_set = None
-            return None
-        if self._graphs:
-            raise ValueError("exposure compensation (exposure_lr) does not combine with capture_step_graphs: the captured "
-                             "step has no exposure launches")
-        if self.bilagrid_set is not None or c.bilagrid_lr > 0:
-            raise ValueError("exposure compensation (exposure_lr) does not combine with bilateral grids (bilagrid_lr): a "
-                             "grid holds the global transform too")
-        from .exposure import ExposureSet
-        self.exposure_set = ExposureSet(views, self.params.flat.device, c.exposure_lr, l2=c.exposure_l2)
-        return self.exposure_set
+        return self._enable_color_set(ExposureSet, views, l2=self.config.exposure_l2)
 
     def enable_bilagrid(self, views):
         """Learn a bilateral grid of colour transforms for each of ``views`` (the full-resolution TRAINING views; held-out
         views are not given and are rendered uncorrected) with the rate, shape and TV weight of the config; -> the
         BilagridSet, or None when the rate is 0."""
         c = self.config
-        if c.bilagrid_lr <= 0:
-            self.bilagrid_set = None
+        return self._enable_color_set(BilagridSet, views, shape=c.bilagrid_shape, tv_weight=c.bilagrid_tv,
+                                      max_steps=c.lr_means_max_steps)
+
+    def _enable_color_set(self, cls, views, **kw):
+        """``color_set`` = ``cls(views, device, the rate of the config, **kw)``, or None when that rate is 0; -> it."""
+        c, cs = self.config, self.color_set
+        if getattr(c, cls.rate_field) <= 0:
+            if isinstance(cs, cls):
+                self.color_set = None
             return None
         if self._graphs:
-            raise ValueError("bilateral grids (bilagrid_lr) do not combine with capture_step_graphs: the captured step has "
-                             "no bilateral-grid launches")
-        if self.exposure_set is not None or c.exposure_lr > 0:
-            raise ValueError("bilateral grids (bilagrid_lr) do not combine with exposure compensation (exposure_lr): a grid "
-                             "holds the global transform too")
-        from .bilagrid import BilagridSet
-        self.bilagrid_set = BilagridSet(views, self.params.flat.device, c.bilagrid_lr, shape=c.bilagrid_shape,
-                                        tv_weight=c.bilagrid_tv, max_steps=c.lr_means_max_steps)
-        return self.bilagrid_set
+            raise ValueError(f"{cls.what} ({cls.rate_field}) cannot be used with capture_step_graphs: the captured step "
+                             "has no launches for it")
+        for other in COLOR_SETS:
+            if other is not cls and (isinstance(cs, other) or getattr(c, other.rate_field) > 0):
+                raise ValueError(f"{cls.what} ({cls.rate_field}) cannot be combined with {other.what} ({other.rate_field}): "
+                                 "a grid holds the global transform too")
+        self.color_set = cls(views, self.params.flat.device, getattr(c, cls.rate_field), **kw)
+        return self.color_set
+
+    exposure_set = property(lambda self: self.color_set if isinstance(self.color_set, ExposureSet) else None)
+    bilagrid_set = property(lambda self: self.color_set if isinstance(self.color_set, BilagridSet) else None)
 
     def enable_pose_refinement(self, views):
         """Refine the poses of ``views`` (the full-resolution TRAINING views; held-out views are not given) with the
@@ -382,19 +382,11 @@ class DepthGaussianSplattingModel:
         if normals:
             out["normal"] = ops.depth_normals(cam, depth_acc, 1.0 - alpha.detach(), self.config.normal_alpha_min,
                                               self.config.normal_max_jump)
-        if exposure_of is not None and self.exposure_set is not None and self.exposure_set.owns(exposure_of):
-            E = self.exposure_set.row(exposure_of)[:12].detach().clone().view(3, 4)
-            out.update(rgb_raw=rgb, rgb=ops.apply_exposure(rgb, E))
-        bs = self.bilagrid_set
-        if bilagrid_of is not None and bs is not None and bs.owns(bilagrid_of):
-            out.update(rgb_raw=rgb, rgb=ops.apply_bilagrid(rgb, self._bilagrid_leaf(bilagrid_of, False)))
+        cs = self.color_set
+        of = exposure_of if isinstance(cs, ExposureSet) else bilagrid_of if isinstance(cs, BilagridSet) else None
+        if of is not None and cs.owns(of):
+            out.update(rgb_raw=rgb, rgb=cs.apply(rgb, cs.leaf(of, False)))
         return out
-
-    def _bilagrid_leaf(self, view, requires_grad: bool) -> torch.Tensor:
-        """A copy of the view's grid as [GH,GW,L,12] for the autograd path."""
-        bs = self.bilagrid_set
-        GW, GH, L = bs.shape
-        return bs.row(view)[:bs.n].detach().clone().view(GH, GW, L, 12).requires_grad_(requires_grad)
 
     def depth_loss(self, depth_acc, alpha, view: View) -> torch.Tensor:
         """mean over valid (D_gt > 0) of (D_hat - D_gt)^2 [ / (uw * U + eps) ]."""
@@ -413,24 +405,15 @@ class DepthGaussianSplattingModel:
     def get_loss_dict(self, outputs, view: View) -> Dict[str, torch.Tensor]:
         c = self.config
         rgb = outputs["rgb"]
-        es = self.exposure_set
-        if es is not None and es.owns(view) and self.step >= c.exposure_start_step and "rgb_raw" not in outputs:
-            # the autograd path of the exposure term: the loss is taken on the compensated image; E is a leaf whose
-            # gradient the caller may read from outputs["exposure"].grad (the fused step learns it on the device)
-            E = outputs["exposure"] = es.row(view)[:12].detach().clone().view(3, 4).requires_grad_(True)
-            rgb = ops.apply_exposure(rgb, E)
-        bs, tv_loss = self.bilagrid_set, None
-        if bs is not None and bs.owns(view) and self.step >= c.bilagrid_start_step and "rgb_raw" not in outputs:
-            # the autograd path of the bilateral grid: the loss is taken on the corrected image; the grid is a leaf whose
-            # gradient the caller may read from outputs["bilagrid"].grad (the fused step learns it on the device)
-            g = outputs["bilagrid"] = self._bilagrid_leaf(view, True)
-            rgb = ops.apply_bilagrid(rgb, g)
-            tv_loss = bs.tv_weight * sum(((g.narrow(a, 1, g.shape[a] - 1) - g.narrow(a, 0, g.shape[a] - 1)) ** 2).mean()
-                                         for a in (0, 1, 2))
+        cs, own_terms = self.color_set, {}
+        if cs is not None and cs.owns(view) and self.step >= getattr(c, cs.start_field) and "rgb_raw" not in outputs:
+            # the autograd path of the colour correction: the loss is taken on the corrected image; its parameters are a leaf
+            # whose gradient the caller may read from outputs[cs.name].grad (the fused step learns them on the device)
+            leaf = outputs[cs.name] = cs.leaf(view, True)
+            rgb = cs.apply(rgb, leaf)
+            own_terms = cs.leaf_loss_terms(leaf)
         l1 = (rgb - view.rgb).abs().mean()
-        loss = {"main_loss": (1 - c.ssim_lambda) * l1}
-        if tv_loss is not None:
-            loss["bilagrid_tv_loss"] = tv_loss
+        loss = {"main_loss": (1 - c.ssim_lambda) * l1, **own_terms}
         if c.ssim_lambda > 0:
             loss["main_loss"] = loss["main_loss"] + c.ssim_lambda * (1 - _SSIM.apply(rgb, view.rgb))
         if c.depth_loss_mult > 0 and view.depth is not None:
@@ -480,16 +463,8 @@ class DepthGaussianSplattingModel:
             dl = self.pose_refiner.deltas()
             m["pose_delta_deg"] = torch.tensor(sum(a for a, _ in dl) / max(len(dl), 1))
             m["pose_delta_m"] = torch.tensor(sum(b for _, b in dl) / max(len(dl), 1))
-        if self.exposure_set is not None and len(self.exposure_set.views) > 0:   # means over the training views
-            E = self.exposure_set.state[:, :12]
-            m["exposure_gain"] = E[:, [0, 5, 10]].mean()
-            m["exposure_offset"] = E[:, [3, 7, 11]].mean()
-        bs = self.bilagrid_set
-        if bs is not None and len(bs.views) > 0:   # means over the training views
-            GW, GH, L = bs.shape
-            g = bs.state[:, :bs.n].view(-1, GH, GW, L, 12)
-            m["bilagrid_tv"] = sum(((g.narrow(a, 1, g.shape[a] - 1) - g.narrow(a, 0, g.shape[a] - 1)) ** 2).mean() for a in (1, 2, 3))
-            m["bilagrid_delta"] = (g - g.new_tensor([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])).abs().mean()
+        if self.color_set is not None:
+            m.update(self.color_set.metrics())
         return m
 
     @torch.no_grad()
@@ -573,57 +548,41 @@ class DepthGaussianSplattingModel:
                 weight=c.normal_prior_mult, accumulate_into=(v_depth, v_alpha) if "mono_stats" in ran else None)
         return ran, v_depth, v_alpha
 
-    def _rgb_loss_backward(self, view: View, cam: Camera, lists, images, v_depth, v_alpha, exposure, guard, may_pipeline: bool,
-                           bilagrid=None):
-        """SSIM + K7, band-pipelined or in sequence (with the view's ``exposure`` or ``bilagrid`` row: SSIM on the corrected
-        image) -> (partials, tile_loss, ssim_sum, expo_out, bila_out); ``lists`` = (splats, group_base, sorted_gid, tile_start),
+    def _rgb_loss_backward(self, view: View, cam: Camera, lists, images, v_depth, v_alpha, color_row, guard, may_pipeline: bool):
+        """SSIM + K7, band-pipelined or in sequence (with the view's ``color_row``: SSIM on the corrected image)
+        -> (partials, tile_loss, ssim_sum, color_out); ``lists`` = (splats, group_base, sorted_gid, tile_start),
         ``images`` = (rgb, depth_acc, final_T)."""
-        c, rgb = self.config, images[0]
+        c, cs, rgb = self.config, self.color_set, images[0]
         w_ssim = -c.ssim_lambda / (3 * cam.H * cam.W)
         spec = self.loss_spec(view)
-        if (exposure is None and bilagrid is None and c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles
+        if (color_row is None and c.ssim_lambda > 0 and c.pipeline_ssim and cam.num_tiles >= c.pipeline_ssim_min_tiles
                 and may_pipeline and not torch.cuda.is_current_stream_capturing()):
             if self._side_stream is None:
                 self._side_stream = torch.cuda.Stream(device=rgb.device)
-            return ops.rasterize_bwd_ssim_pipelined(cam, *lists, *images, view.rgb, w_ssim, spec, self._side_stream) + (None, None)
-        ssim_sum = v_rgb = expo_out = bila_out = None
-        bs = self.bilagrid_set
-        img = rgb if exposure is None else ops.exposure_fwd(rgb, exposure)
-        if bilagrid is not None:
-            img = ops.bilagrid_fwd(rgb, bilagrid, bs.shape)
+            return ops.rasterize_bwd_ssim_pipelined(cam, *lists, *images, view.rgb, w_ssim, spec, self._side_stream) + (None,)
+        ssim_sum = v_rgb = color_out = None
+        img = rgb if color_row is None else cs.forward(rgb, color_row)
         if c.ssim_lambda > 0:
             ssim_sum, v_rgb = ops.ssim_fwd_bwd(img, view.rgb, weight=w_ssim, reduce=False)
-        if exposure is not None:    # forms the L1 term on the compensated image, hands K7 its upstream image, steps the row
-            es = self.exposure_set
-            expo_out, v_rgb = ops.exposure_bwd(rgb, exposure, gt=view.rgb, l1_weight=spec["l1_weight"], v_img=v_rgb,
-                                               guard=guard, state=exposure, adam=es.adam,
-                                               out=(torch.empty(ops._lib.EXPO_OUT, dtype=torch.float32, device=rgb.device),
-                                                    es.scratch(cam.W, cam.H)))
+        if color_row is not None:   # forms the L1 term on the corrected image, hands K7 its upstream image, steps the row
+            color_out, v_rgb = cs.backward_step(rgb, color_row, view.rgb, spec["l1_weight"], v_rgb, guard, self.step,
+                                                cam.W, cam.H)
             spec.update(gt_rgb=None, l1_weight=0.0)     # the L1 term went in through v_rgb; the depth terms stay fused
-        if bilagrid is not None:    # likewise: the L1 term on the corrected image, K7's upstream image, the row's step
-            bila_out, v_rgb, _ = ops.bilagrid_bwd(rgb, bilagrid, bs.shape, gt=view.rgb, l1_weight=spec["l1_weight"], v_img=v_rgb,
-                                                  tv_weight=bs.tv_weight, guard=guard, state=bilagrid, adam=bs.adam(self.step),
-                                                  want_grad=False,
-                                                  out=(torch.empty(ops._lib.BILAGRID_OUT, dtype=torch.float32, device=rgb.device),
-                                                       bs.scratch(cam.W, cam.H)))
-            spec.update(gt_rgb=None, l1_weight=0.0)
         partials, tile_loss = ops.rasterize_bwd(cam, *lists, *images, v_rgb=v_rgb, v_depth=v_depth, v_alpha=v_alpha,
                                                 loss=spec, want_tile_loss=True)
-        return partials, tile_loss, ssim_sum, expo_out, bila_out
+        return partials, tile_loss, ssim_sum, color_out
 
     def forward_backward(self, view: View, want_v_xy: bool = False, fuse_adam: bool = False,
                          color_block: Optional[torch.Tensor] = None, begin_step: bool = True,
                          colors=None, prefetch=None, next_front=None, pose_grad: bool = False,
-                         exposure: Optional[torch.Tensor] = None, bilagrid: Optional[torch.Tensor] = None):
+                         color_row: Optional[torch.Tensor] = None):
         """Forward + loss + backward of one view into ``params.grad`` (overwritten) -- or, with
         ``fuse_adam``, straight through the optimizer update (K8+K9 fused, ``params.grad`` untouched).
         ``pose_grad``: also ``last["pose_grad"]`` = ``ops.pose_grad`` of this frame, launched before the optimizer
         kernel changes the parameters it was rendered with.
-        ``exposure``: the [48] row of the view's exposure (``ExposureSet.row``): the RGB loss is taken on the compensated
-        image C' = A rgb + b -- ``ops.exposure_fwd``, SSIM on C', ``ops.exposure_bwd`` (which forms the L1 term, hands K7
-        its upstream image and steps the row), K7 without its fused L1 term -- and ``last["exposure"]`` = its [32] result.
-        ``bilagrid``: the [3n+16] row of the view's bilateral grid (``BilagridSet.row``): the same seam with
-        ``ops.bilagrid_fwd`` / ``ops.bilagrid_bwd``, and ``last["bilagrid"]`` = its [8] result.
+        ``color_row``: the view's row in ``color_set`` (``ViewColorSet.row``): the RGB loss is taken on the corrected image
+        C' -- the set's ``forward``, SSIM on C', its ``backward_step`` (which forms the L1 term, hands K7 its upstream image
+        and steps the row), K7 without its fused L1 term -- and ``last[color_set.name]`` = the result vector of that call.
         No host sync unless ``budget.sync``.  Returns device tensors (l1+depth tile losses, ssim sum)."""
         p, cam, deg = self.params, self.tuned(view.cam), self.active_sh_degree()
         splats, radii, group_base, tile_start, sorted_gid, status = ops.project_bin_sort(
@@ -632,17 +591,13 @@ class DepthGaussianSplattingModel:
         guard = None if self.budget.sync else status   # overflowed frame => optimizer kernels are no-ops
         rgb, depth_acc, fT, fidx = ops.rasterize_fwd(cam, splats, sorted_gid, tile_start, opts=self.tuning.raster_opts())
         ran, v_depth, v_alpha = self._image_terms(view, cam, depth_acc, fT)
-        if exposure is not None and color_block is not None:
-            raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps")
-        if bilagrid is not None and color_block is not None:
-            raise ValueError("bilateral grids (bilagrid_lr) are not supported in data-parallel steps")
-        partials, tile_loss, ssim_sum, expo_out, bila_out = self._rgb_loss_backward(
-            view, cam, (splats, group_base, sorted_gid, tile_start), (rgb, depth_acc, fT), v_depth, v_alpha, exposure, guard,
-            may_pipeline=not ran, bilagrid=bilagrid)
-        if expo_out is not None:
-            ran["exposure"] = expo_out
-        if bila_out is not None:
-            ran["bilagrid"] = bila_out
+        if color_row is not None and color_block is not None:
+            raise ValueError(f"{self.color_set.what} ({self.color_set.rate_field}) cannot be used in data-parallel steps")
+        partials, tile_loss, ssim_sum, color_out = self._rgb_loss_backward(
+            view, cam, (splats, group_base, sorted_gid, tile_start), (rgb, depth_acc, fT), v_depth, v_alpha, color_row, guard,
+            may_pipeline=not ran)
+        if color_out is not None:
+            ran[self.color_set.name] = color_out
         if pose_grad:
             if color_block is not None:
                 raise ValueError("pose refinement (pose_lr_rot / pose_lr_trans) is not supported in data-parallel steps")
@@ -679,28 +634,24 @@ class DepthGaussianSplattingModel:
     def loss_from(self, tile_loss, ssim_sum, view: View, mono_stats=None, exposure=None, bilagrid=None) -> Dict[str, torch.Tensor]:
         """The loss values of a fused step from what ``forward_backward`` returned.  ``mono_stats``: the statistics of the
         monocular depth term; default = those of the last ``forward_backward`` when ``tile_loss`` is that call's.
-        ``exposure``: the [32] result of the step's ``ops.exposure_bwd`` (``last["exposure"]``) when the step compensated the
-        view's exposure -- its L1 value is then in that result, not in ``tile_loss``; the same default.  A caller that
-        keeps a ``tile_loss`` beyond its step, or passes a copy of it, keeps and passes that step's ``last["exposure"]`` too.
-        ``bilagrid``: likewise the [8] result of the step's ``ops.bilagrid_bwd`` (``last["bilagrid"]``): its L1 value joins
-        ``main_loss`` and ``bilagrid_tv_loss`` = bilagrid_tv x its TV value."""
+        ``exposure`` / ``bilagrid``: the [32] / [8] result of the step's ``ops.exposure_bwd`` / ``ops.bilagrid_bwd``
+        (``last["exposure"]`` / ``last["bilagrid"]``) when the step corrected the view's colours -- its L1 value is then in that
+        result, not in ``tile_loss``, and ``bilagrid_tv_loss`` = bilagrid_tv x its TV value; the same default.  A caller that
+        keeps a ``tile_loss`` beyond its step, or passes a copy of it, keeps and passes that step's result too."""
         c = self.config
         H, W = view.rgb.shape[:2]
         t = tile_loss.sum(0)
         main = t[0]
-        if exposure is None and self.last.get("tile_loss") is tile_loss:
-            exposure = self.last.get("exposure")
-        if exposure is not None:
-            main = main + exposure[25]     # the L1 term was taken on the compensated image: K7's column is 0
-        if bilagrid is None and self.last.get("tile_loss") is tile_loss:
-            bilagrid = self.last.get("bilagrid")
-        if bilagrid is not None:
-            main = main + bilagrid[1]      # likewise
+        kind, result = (ExposureSet, exposure) if exposure is not None else (BilagridSet, bilagrid)
+        if result is None and self.color_set is not None and self.last.get("tile_loss") is tile_loss:
+            kind, result = type(self.color_set), self.last.get(self.color_set.name)
+        if result is not None:
+            main = main + kind.l1_value(result)     # the L1 term was taken on the corrected image: K7's column is 0
         if ssim_sum is not None:   # per-block partial sums (or an already reduced scalar)
             main = main + c.ssim_lambda * (1 - ssim_sum.sum() / (3 * H * W))
         out = {"main_loss": main, "depth_loss": t[1]}
-        if bilagrid is not None:
-            out["bilagrid_tv_loss"] = c.bilagrid_tv * bilagrid[3]
+        if result is not None:
+            out.update(kind.loss_terms(result, c))
         if mono_stats is None and self.last.get("tile_loss") is tile_loss:
             mono_stats = self.last.get("mono_stats")
         if mono_stats is not None:
@@ -928,12 +879,10 @@ class DepthGaussianSplattingModel:
         if self.pose_refiner is not None or self.config.pose_lr_rot > 0 or self.config.pose_lr_trans > 0:
             raise ValueError("capture_step_graphs does not combine with pose refinement (pose_lr_rot / pose_lr_trans): a "
                              "captured graph bakes the camera in")
-        if self.exposure_set is not None or self.config.exposure_lr > 0:
-            raise ValueError("capture_step_graphs does not combine with exposure compensation (exposure_lr): the captured "
-                             "step has no exposure launches")
-        if self.bilagrid_set is not None or self.config.bilagrid_lr > 0:
-            raise ValueError("capture_step_graphs does not combine with bilateral grids (bilagrid_lr): the captured step has "
-                             "no bilateral-grid launches")
+        for kind in COLOR_SETS:
+            if isinstance(self.color_set, kind) or getattr(self.config, kind.rate_field) > 0:
+                raise ValueError(f"capture_step_graphs does not combine with {kind.what} ({kind.rate_field}): the captured "
+                                 "step has no launches for it")
         if self.mcmc is not None or mcmc_configured(self.config):
             raise ValueError("capture_step_graphs does not combine with the MCMC strategy (enable_mcmc / opacity_reg, scale_reg, "
                              "mcmc_noise_lr): the captured step is the fused one and has no noise draw")
@@ -973,7 +922,7 @@ class DepthGaussianSplattingModel:
         between the two calls except through this class."""
         distributed = dp is not None and dp.active
         opt, density = self.optimizer, self.density
-        pose_on, expo_row, bila_row, next_view = self._begin_refiners(view, next_view, distributed)
+        pose_on, color_row, next_view = self._begin_refiners(view, next_view, distributed)
         full_view = view    # what the speculative budget replays (the schedule is applied again on the replay)
         view, next_view = self._apply_schedule(view, next_view)
         deg = self.active_sh_degree()
@@ -1002,8 +951,7 @@ class DepthGaussianSplattingModel:
         arm = self._arm_prefetch(next_view, deg, fuse, factored, in_use=colors if fuse else pre)
         self.forward_backward(view, want_v_xy=density is not None and mcmc is None, fuse_adam=fuse, color_block=block,
                               colors=colors, prefetch=arm if fuse else None,
-                              next_front=arm.front if arm is not None else None, pose_grad=pose_on, exposure=expo_row,
-                              bilagrid=bila_row)
+                              next_front=arm.front if arm is not None else None, pose_grad=pose_on, color_row=color_row)
         self._prefetch_ready = arm
         if pose_on:     # taken at the (possibly downscaled) camera, applied to the full-resolution view's pose
             self.pose_refiner.submit(full_view, self.last["pose_grad"])
@@ -1031,8 +979,7 @@ class DepthGaussianSplattingModel:
             self._refine(dp)
 
     def _begin_refiners(self, view: View, next_view: Optional[View], distributed: bool):
-        """Checks and pending updates of the pose refiner, the exposure set and the bilateral grids
-        -> (pose_on, expo_row or None, bila_row or None, next_view or None)."""
+        """Checks and pending updates of the pose refiner and the colour set -> (pose_on, color_row or None, next_view or None)."""
         ref, pose_on = self.pose_refiner, False
         if ref is None and (self.config.pose_lr_rot > 0 or self.config.pose_lr_trans > 0):
             raise ValueError("pose_lr_rot / pose_lr_trans are set but no view is registered for refinement: call "
@@ -1048,28 +995,17 @@ class DepthGaussianSplattingModel:
             if next_view is not None:
                 ref.apply_pending(next_view, self)
             pose_on = ref.owns(view) and self.step >= self.config.pose_start_step
-        es, expo_row = self.exposure_set, None
-        if es is None and self.config.exposure_lr > 0:
-            raise ValueError("exposure_lr is set but no view is registered for exposure compensation: call "
-                             "model.enable_exposure(training_views) before the first train_step")
-        if es is not None:
+        cs, color_row = self.color_set, None
+        for kind in COLOR_SETS:
+            if getattr(self.config, kind.rate_field) > 0 and not isinstance(cs, kind):
+                raise ValueError(f"{kind.rate_field} is set but no view is registered for {kind.what}: call "
+                                 f"model.enable_{kind.name}(training_views) before the first train_step")
+        if cs is not None:
             if distributed:
-                raise ValueError("exposure compensation (exposure_lr) is not supported in data-parallel steps (dp.active)")
-            if es.owns(view) and self.step >= self.config.exposure_start_step:
-                expo_row = es.row(view)     # of the full-resolution view: its downscaled forms step the same row
-        bs, bila_row = self.bilagrid_set, None
-        if bs is None and self.config.bilagrid_lr > 0:
-            raise ValueError("bilagrid_lr is set but no view is registered for bilateral grids: call "
-                             "model.enable_bilagrid(training_views) before the first train_step")
-        if bs is not None:
-            if distributed:
-                raise ValueError("bilateral grids (bilagrid_lr) are not supported in data-parallel steps (dp.active)")
-            if es is not None:
-                raise ValueError("bilateral grids (bilagrid_lr) do not combine with exposure compensation (exposure_lr): a grid "
-                                 "holds the global transform too")
-            if bs.owns(view) and self.step >= self.config.bilagrid_start_step:
-                bila_row = bs.row(view)     # of the full-resolution view: its downscaled forms step the same row
-        return pose_on, expo_row, bila_row, next_view
+                raise ValueError(f"{cs.what} ({cs.rate_field}) cannot be used in data-parallel steps (dp.active)")
+            if cs.owns(view) and self.step >= getattr(self.config, cs.start_field):
+                color_row = cs.row(view)    # of the full-resolution view: its downscaled forms step the same row
+        return pose_on, color_row, next_view
 
     def _apply_schedule(self, view: View, next_view: Optional[View]):
         """The recent cameras, the learning rate of the means, the coarse-to-fine level -> (view, next_view) at their levels."""
@@ -1219,10 +1155,8 @@ class DepthGaussianSplattingModel:
                   optim=self.optimizer.state_dict(), config=dataclasses.asdict(self.config))
         if self.pose_refiner is not None:   # only then: checkpoints of runs without refinement keep their keys
             sd["pose"] = self.pose_refiner.state_dict(self)
-        if self.exposure_set is not None:   # likewise
-            sd["exposure"] = self.exposure_set.state_dict()
-        if self.bilagrid_set is not None:   # likewise
-            sd["bilagrid"] = self.bilagrid_set.state_dict()
+        if self.color_set is not None:      # likewise
+            sd[self.color_set.name] = self.color_set.state_dict()
         if self.mcmc is not None:           # likewise: the noise stream goes on where it stopped
             sd["mcmc"] = dict(generator=self._mcmc_gen.get_state())
         return sd
@@ -1248,12 +1182,11 @@ class DepthGaussianSplattingModel:
         self.optimizer.load_state_dict(sd["optim"])
         if self.pose_refiner is not None and sd.get("pose") is not None:
             self.pose_refiner.load_state_dict(sd["pose"], self)
-        # a model WITHOUT a set ignores the key on purpose: evaluation and export load a compensated run's checkpoint
-        # and render every view uncompensated (held-out views have no row); a set of another size is refused by the set
-        if self.exposure_set is not None and sd.get("exposure") is not None:
-            self.exposure_set.load_state_dict(sd["exposure"])
-        if self.bilagrid_set is not None and sd.get("bilagrid") is not None:    # the same rule
-            self.bilagrid_set.load_state_dict(sd["bilagrid"])
+        # a model WITHOUT a set ignores the key on purpose: evaluation and export load a corrected run's checkpoint
+        # and render every view uncorrected (held-out views have no row); a set of another size is refused by the set
+        cs = self.color_set
+        if cs is not None and sd.get(cs.name) is not None:
+            cs.load_state_dict(sd[cs.name])
         if self.mcmc is not None and sd.get("mcmc") is not None:
             self._mcmc_gen.set_state(sd["mcmc"]["generator"].cpu())
 

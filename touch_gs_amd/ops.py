@@ -1198,27 +1198,38 @@ def _expo_row(expo, what: str):
     return expo
 
 
-def _expo_buf(t, n: int, what: str, dev, dtype=torch.float32, exact: bool = False):
-    """A buffer a kernel writes (or the guard it reads): on the frame's device, contiguous, of the dtype and size it assumes."""
+def _dev_buf(t, n: int, who: str, what: str, dev, dtype=torch.float32, exact: bool = False):
+    """A buffer a kernel of ``who`` writes (or the guard it reads): on the frame's device, contiguous, of the dtype and size
+    it assumes."""
     if (not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or not t.is_contiguous()
             or (t.numel() != n if exact else t.numel() < n)):
-        raise ValueError(f"exposure_bwd: {what} must be a contiguous {dtype} tensor on {dev} of "
+        raise ValueError(f"{who}: {what} must be a contiguous {dtype} tensor on {dev} of "
                          f"{'' if exact else 'at least '}{n} elements")
     return t
+
+
+def _rgb_images(who: str, rgb, gt=None, v_img=None, out=None):
+    """The images of a colour-correction op of ``who`` -> (rgb [H,W,3] detached, gt, v_img, out): float32 and contiguous,
+    ``gt`` / ``v_img`` of rgb's shape or None, ``out`` a caller's image of rgb's shape or None."""
+    rgb, gt, v_img = _f32c(rgb.detach()), _f32c(gt), _f32c(v_img)
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"{who}: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    for name, t in (("gt", gt), ("v_img", v_img)):
+        if t is not None and t.shape != rgb.shape:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} does not match rgb {tuple(rgb.shape)}")
+    if out is not None and (out.device != rgb.device or out.dtype != torch.float32 or not out.is_contiguous()
+                            or out.shape != rgb.shape):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor of rgb's shape on rgb's device")
+    return rgb, gt, v_img, out
 
 
 def exposure_fwd(rgb, expo, out=None):
     """-> C' [H,W,3] with C'[p][c] = sum_k A[c][k] rgb[p][k] + b[c]; ``expo`` = E = [A | b] on the device ([3,4], [12] or a
     view's [48] state row).  No clamp.  No host sync.  (tgs_exposure_fwd)"""
     lib = _lib.load()
-    rgb = _f32c(rgb.detach())
-    if rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError(f"exposure_fwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    rgb, _, _, out = _rgb_images("exposure_fwd", rgb, out=out)
     H, W = rgb.shape[0], rgb.shape[1]
-    if out is None:
-        out = torch.empty_like(rgb)
-    elif out.device != rgb.device or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != rgb.shape:
-        raise ValueError("exposure_fwd: out must be a contiguous float32 tensor of rgb's shape on rgb's device")
+    out = torch.empty_like(rgb) if out is None else out
     check(lib.tgs_exposure_fwd(W, H, ptr(rgb), ptr(_expo_row(expo, "exposure_fwd")), ptr(out), _stream()), "tgs_exposure_fwd")
     return out
 
@@ -1233,12 +1244,8 @@ def exposure_bwd(rgb, expo, gt=None, l1_weight: float = 0.0, v_img=None, guard=N
     stepped in the same call with ``adam = dict(lr, betas, eps, l2)``; None = gradient only.  ``expo`` may be ``state``.
     ``out`` = (result [32], scratch [tgs_exposure_num_partials, 32]) to allocate nothing but ``v_rgb``.  No host sync."""
     lib = _lib.load()
-    rgb, gt, v_img = _f32c(rgb.detach()), _f32c(gt), _f32c(v_img)
-    if rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError(f"exposure_bwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
-    for name, t in (("gt", gt), ("v_img", v_img)):
-        if t is not None and t.shape != rgb.shape:
-            raise ValueError(f"exposure_bwd: {name} {tuple(t.shape)} does not match rgb {tuple(rgb.shape)}")
+    who = "exposure_bwd"
+    rgb, gt, v_img, _ = _rgb_images(who, rgb, gt, v_img)
     H, W = rgb.shape[0], rgb.shape[1]
     dev = rgb.device
     P = lib.tgs_exposure_num_partials(W, H)
@@ -1246,15 +1253,15 @@ def exposure_bwd(rgb, expo, gt=None, l1_weight: float = 0.0, v_img=None, guard=N
         out = (torch.empty(_lib.EXPO_OUT, dtype=torch.float32, device=dev),
                torch.empty(P, _lib.EXPO_OUT, dtype=torch.float32, device=dev))
     res, scratch = out
-    _expo_buf(res, _lib.EXPO_OUT, "out[0] (the result)", dev, exact=True)
-    _expo_buf(scratch, P * _lib.EXPO_OUT, "out[1] (the scratch, [tgs_exposure_num_partials(W, H), 32])", dev)
+    _dev_buf(res, _lib.EXPO_OUT, who, "out[0] (the result)", dev, exact=True)
+    _dev_buf(scratch, P * _lib.EXPO_OUT, who, "out[1] (the scratch, [tgs_exposure_num_partials(W, H), 32])", dev)
     if guard is not None:
-        _expo_buf(guard, 2, "guard (the frame's status word)", dev, dtype=torch.int32)
+        _dev_buf(guard, 2, who, "guard (the frame's status word)", dev, dtype=torch.int32)
     lr = b1 = b2 = eps = l2 = 0.0
     if state is not None:
         if adam is None:
             raise ValueError("exposure_bwd: a state row needs adam = dict(lr, betas, eps, l2)")
-        _expo_buf(state, _lib.EXPO_STATE, "state (a view's row)", dev, exact=True)
+        _dev_buf(state, _lib.EXPO_STATE, who, "state (a view's row)", dev, exact=True)
         lr, (b1, b2), eps, l2 = adam["lr"], adam.get("betas", (0.9, 0.999)), adam.get("eps", 1e-15), adam.get("l2", 0.0)
     v_rgb = torch.empty_like(rgb)
     check(lib.tgs_exposure_bwd(W, H, ptr(rgb), ptr(_expo_row(expo, "exposure_bwd")), ptr(gt), C.c_float(l1_weight), ptr(v_img),
@@ -1310,29 +1317,16 @@ def _bila_grid(grid, shape, what: str):
     return grid
 
 
-def _bila_buf(t, n: int, what: str, dev, dtype=torch.float32, exact: bool = False):
-    if (not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or not t.is_contiguous()
-            or (t.numel() != n if exact else t.numel() < n)):
-        raise ValueError(f"bilagrid_bwd: {what} must be a contiguous {dtype} tensor on {dev} of "
-                         f"{'' if exact else 'at least '}{n} elements")
-    return t
-
-
 def bilagrid_fwd(rgb, grid, shape, out=None):
     """-> C' [H,W,3]: ``rgb`` through the bilateral grid ``grid`` ([GH,GW,L,12], the last axis a row-major 3x4 [A | b]; or a
     view's state row) of ``shape`` = (GW, GH, L), sliced trilinearly at the pixel's position and the luminance of its
     colour.  No clamp.  No host sync.  (tgs_bilagrid_fwd)"""
     lib = _lib.load()
-    rgb = _f32c(rgb.detach())
-    if rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError(f"bilagrid_fwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
+    rgb, _, _, out = _rgb_images("bilagrid_fwd", rgb, out=out)
     H, W = rgb.shape[0], rgb.shape[1]
     GW, GH, L = (int(x) for x in shape)
     bilagrid_sizes(W, H, shape)
-    if out is None:
-        out = torch.empty_like(rgb)
-    elif out.device != rgb.device or out.dtype != torch.float32 or not out.is_contiguous() or out.shape != rgb.shape:
-        raise ValueError("bilagrid_fwd: out must be a contiguous float32 tensor of rgb's shape on rgb's device")
+    out = torch.empty_like(rgb) if out is None else out
     check(lib.tgs_bilagrid_fwd(W, H, GW, GH, L, ptr(rgb), ptr(_bila_grid(grid, shape, "bilagrid_fwd")), ptr(out), _stream()),
           "tgs_bilagrid_fwd")
     return out
@@ -1352,12 +1346,8 @@ def bilagrid_bwd(rgb, grid, shape, gt=None, l1_weight: float = 0.0, v_img=None, 
     ``out`` = (result [8], scratch [>= bilagrid_sizes(W, H, shape)[1]]) to allocate nothing but ``v_rgb`` and ``grad``;
     (result, scratch, v_rgb [H,W,3]) or (result, scratch, v_rgb, grad [2, n]) to allocate nothing.  No host sync."""
     lib = _lib.load()
-    rgb, gt, v_img = _f32c(rgb.detach()), _f32c(gt), _f32c(v_img)
-    if rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError(f"bilagrid_bwd: rgb must be [H,W,3], got {tuple(rgb.shape)}")
-    for name, t in (("gt", gt), ("v_img", v_img)):
-        if t is not None and t.shape != rgb.shape:
-            raise ValueError(f"bilagrid_bwd: {name} {tuple(t.shape)} does not match rgb {tuple(rgb.shape)}")
+    who = "bilagrid_bwd"
+    rgb, gt, v_img, _ = _rgb_images(who, rgb, gt, v_img)
     H, W = rgb.shape[0], rgb.shape[1]
     GW, GH, L = (int(x) for x in shape)
     dev = rgb.device
@@ -1365,23 +1355,23 @@ def bilagrid_bwd(rgb, grid, shape, gt=None, l1_weight: float = 0.0, v_img=None, 
     if out is None:
         out = (torch.empty(_lib.BILAGRID_OUT, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev))
     res, scratch = out[0], out[1]
-    _bila_buf(res, _lib.BILAGRID_OUT, "out[0] (the result)", dev, exact=True)
-    _bila_buf(scratch, S, "out[1] (the scratch, tgs_bilagrid_scratch_floats floats)", dev)
+    _dev_buf(res, _lib.BILAGRID_OUT, who, "out[0] (the result)", dev, exact=True)
+    _dev_buf(scratch, S, who, "out[1] (the scratch, tgs_bilagrid_scratch_floats floats)", dev)
     if guard is not None:
-        _bila_buf(guard, 2, "guard (the frame's status word)", dev, dtype=torch.int32)
+        _dev_buf(guard, 2, who, "guard (the frame's status word)", dev, dtype=torch.int32)
     lr = b1 = b2 = eps = 0.0
     if state is not None:
         if adam is None:
             raise ValueError("bilagrid_bwd: a state row needs adam = dict(lr, betas, eps)")
-        _bila_buf(state, 3 * n + _lib.BILAGRID_TAIL, "state (a view's row)", dev, exact=True)
+        _dev_buf(state, 3 * n + _lib.BILAGRID_TAIL, who, "state (a view's row)", dev, exact=True)
         lr, (b1, b2), eps = adam["lr"], adam.get("betas", (0.9, 0.999)), adam.get("eps", 1e-15)
     elif not want_grad:
         raise ValueError("bilagrid_bwd: want_grad=False needs a state row to step")
     grad = None
     if want_grad:
-        grad = _bila_buf(out[3], 2 * n, "out[3] (grad, [2, n])", dev, exact=True) if len(out) > 3 else \
+        grad = _dev_buf(out[3], 2 * n, who, "out[3] (grad, [2, n])", dev, exact=True) if len(out) > 3 else \
             torch.empty(2, n, dtype=torch.float32, device=dev)
-    v_rgb = _bila_buf(out[2], rgb.numel(), "out[2] (v_rgb)", dev, exact=True) if len(out) > 2 else torch.empty_like(rgb)
+    v_rgb = _dev_buf(out[2], rgb.numel(), who, "out[2] (v_rgb)", dev, exact=True) if len(out) > 2 else torch.empty_like(rgb)
     check(lib.tgs_bilagrid_bwd(W, H, GW, GH, L, ptr(rgb), ptr(_bila_grid(grid, shape, "bilagrid_bwd")), ptr(gt),
                                C.c_float(l1_weight), ptr(v_img), C.c_float(tv_weight), ptr(v_rgb), ptr(scratch), ptr(grad),
                                ptr(res), ptr(guard), ptr(state), C.c_float(lr), C.c_float(b1), C.c_float(b2), C.c_float(eps),

@@ -426,12 +426,8 @@ def main(argv=None, view_hook=None):
             if model.pose_refiner is not None:
                 from .pose import save_refined_poses
                 save_refined_poses(run_dir, model.pose_refiner, train_names)
-            if model.exposure_set is not None:
-                from .exposure import save_exposures
-                save_exposures(run_dir, model.exposure_set, train_names)
-            if model.bilagrid_set is not None:
-                from .bilagrid import save_bilagrids
-                save_bilagrids(run_dir, model.bilagrid_set, train_names)
+            if model.color_set is not None:     # exposures.json / bilagrids.npz
+                model.color_set.save(run_dir, train_names)
     model.flush()
     if dp.world > 1:
         dp.assert_replicas_identical(model.params.flat)
